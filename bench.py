@@ -3,10 +3,12 @@
 
   --config cfg3 (default)  configs[2] (N = 1) / configs[3] (N > 1, strong scaling) of BASELINE.json, the configuration "bins/hour
                            (lineage_wf-equiv)" is quoted on: see below.  One step = one lineage_wf-equivalent pass over ALL --bins-total
-                           bins.  A step lasts tens of seconds, so the number of timed steps is min(--steps, what fits --budget-seconds
-                           judged from the warm pass): the line carries `steps` (run) and `steps_requested`.  At N = 1 the same line
-                           carries `cfg2` (a short run of the configuration below), `cpu_baseline` (the CPU oracle on sampled bins with
-                           their lineage's model subsets) and `emulated_ranks_of_8` (see --emulate-rank).
+                           bins; --warmup whole steps run untimed, then exactly --steps timed ones.  A plain run does only that and prints
+                           the headline line; --full adds the side measurements after the timed steps (at N = 1: `cfg2`, a short run of
+                           the configuration below, `cpu_baseline`, the CPU oracle on sampled bins with their lineage's model subsets,
+                           `emulated_ranks_of_8`, the gene-calling legs, the harder world, `verify`, the roofline figures).
+  --dump-outputs DIR       cfg3: after the timed steps, what the last step computed as DIR/<name>.npy (float64): the QA table of every
+                           bin and the domtblout rows of both passes for a fixed sample of the bins (see dump_outputs).
   --config cfg2            configs[1] of BASELINE.json: cpr_43-shaped 43-profile DB against 100 synthetic 2 Mb bins (~2k ORFs
                            each) PER GPU.  One step = one pass of the hot path (scan + reduce + the one gather of QA rows) over the
                            rank's bins, inputs resident in HBM.  `--scaling strong --bins-total N` shards N bins over the ranks.
@@ -52,8 +54,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", choices=["cfg2", "cfg3", "cfg5", "genes", "fasta", "emulate8"], default="cfg3")
-    ap.add_argument("--budget-seconds", type=float, default=float(os.environ.get("CKM_BENCH_BUDGET_S", "240")),
-                    help="cfg3: wall-clock budget of the timed region; the steps actually run are min(--steps, budget / estimated step)")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg3: after the timed steps, also the side measurements (cfg2, CPU baselines, emulated ranks, gene calling, harder world, "
+                         "verify against the CPU oracle, roofline and device-state figures); off: the headline line alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="cfg3: write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--emulate-rank", default=None, help="cfg3: R/W -- run as rank R of W on this one GPU (no collectives)")
     ap.add_argument("--no-cfg2", action="store_true", help="cfg3: skip the nested cfg2 measurement")
     ap.add_argument("--no-emulation", action="store_true", help="cfg3: skip the nested rank-0-of-8 emulation")
@@ -67,7 +72,7 @@ def parse():
     ap.add_argument("--no-genes", action="store_true", help="cfg3: skip the gene-calling side legs (gene_front_end, gene_calling, from_fasta)")
     ap.add_argument("--from-fasta-bins", type=int, default=512, help="cfg3 / genes: bins of the from_fasta leg (nucleotide bins -> genes -> tree pass -> analyze pass -> qa table); 0 skips it.  256 bins are mostly the ramp of the calls in flight (31 - 34 s per 1000), 512 read 28 s, 1000 read 27.4 s (profiles/r05C, r05w)")
     ap.add_argument("--hard-bins", type=int, default=128, help="cfg3: bins of the hard_workload side leg (the lineage pass over a HARDER synthetic world: per-bin composition skew, 5 %% low-complexity ORFs, 3-5 diverged paralogs per planted marker -- synthdata/synth_lineage.py: make_lineage_bin(hard=True)); 0 skips it")
-    ap.add_argument("--verify", type=int, default=3, help="cfg3 / cfg5: bins of the last timed step whose written tables are diffed against the CPU oracle after the timed region (0 = off)")
+    ap.add_argument("--verify", type=int, default=3, help="cfg3 (with --full) / cfg5: bins of the last timed step whose written tables are diffed against the CPU oracle after the timed region (0 = off)")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--pipeline", type=int, default=1,
                     help="cfg2: steps in flight at once (own context each); 1 = every step runs alone")
@@ -220,10 +225,10 @@ def lineage_setup(workdir, nbins, rank, world, sync):
     from synthdata import synth, synth_lineage as sl
     from checkm_amd.defaultValues import DefaultValues
     data = os.path.join(workdir, "lineage_data")
-    if rank == 0:
-        sl.World(data)
+    w = sl.World(data) if rank == 0 else None
     sync()
-    w = sl.World(data, write=False)
+    if w is None:
+        w = sl.World(data, write=False)
     DefaultValues.set_data_root(data)
     binIds = ["bin_%04d" % b for b in range(nbins)]
     files = [os.path.join(workdir, "%s.faa" % b) for b in binIds]
@@ -269,6 +274,46 @@ def lineage_pass(w, binIds, files, lin, out, rank, called=True):
     mgf.release_scan(out, background=True)          # (the memory of the scans is returned by a helper thread while the next pass starts; the next release waits for it, find() does not)
     t5 = time.perf_counter()
     return {"tree_find_s": t1 - t0, "analyze_find_s": t2 - t1, "qa_s": t3 - t2, "total_s": t3 - t0, "drop_python_objects_s": t4 - t3, "release_call_s": t5 - t4}, tot
+
+
+DUMP_BYTES_MAX = 64 << 20
+DUMP_SAMPLE_BINS = 128
+HIT_COLUMNS = ("bin", "table", "contig", "orf", "model", "tlen", "qlen", "full_evalue", "full_score", "full_bias", "dom_index", "dom_count", "c_evalue",
+               "i_evalue", "dom_score", "dom_bias", "hmm_from", "hmm_to", "ali_from", "ali_to", "env_from", "env_to", "acc")
+
+
+def dump_outputs(dump_dir, w, out_dir, binIds, seed=12345):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float64 arrays under `dump_dir`.
+      qa.npy    the QA table of every bin (printSummary's numeric columns, one row per bin in bin order; column 0 = bin index)
+      hits.npy  the domtblout rows of both passes (table 0 = hmmer.tree.txt, 1 = hmmer.analyze.txt) of a fixed, seeded sample of the bins,
+                in file order; names become numbers: contig and ORF of the target (c<contig>_<orf>), model index in checkm.hmm (phylo.hmm
+                models after them).  Columns: HIT_COLUMNS.  The sample shrinks from its end if the arrays would pass 64 MB."""
+    from checkm_amd.defaultValues import DefaultValues
+    os.makedirs(dump_dir, exist_ok=True)
+    bin_index = {b: k for k, b in enumerate(binIds)}
+    with open(os.path.join(out_dir, "qa_table.tsv")) as f:
+        rows = [ln.rstrip("\n").split("\t") for ln in f.read().split("\n")[1:] if ln.strip()]
+    qa = np.array(sorted([float(bin_index[r[0]])] + [float(x) for x in r[2:]] for r in rows), dtype=np.float64)
+    model = {p.name: k for k, p in enumerate(w.profs)}
+    model.update({p.name: len(w.profs) + k for k, p in enumerate(w.phylo)})
+    sample = sorted(np.random.default_rng(seed).permutation(len(binIds))[:DUMP_SAMPLE_BINS].tolist())
+    per_bin = []
+    for b in sample:
+        hits = []
+        for t, table in enumerate((DefaultValues.HMMER_TABLE_PHYLO_OUT, DefaultValues.HMMER_TABLE_OUT)):
+            with open(os.path.join(out_dir, "bins", binIds[b], table)) as f:
+                for ln in f:
+                    if ln.startswith("#") or not ln.strip():
+                        continue
+                    v = ln.split(None, 22)
+                    contig, orf = v[0][1:].split("_")
+                    hits.append([b, t, int(contig), int(orf), model[v[3]], float(v[2]), float(v[5])] + [float(x) for x in v[6:22]])
+        per_bin.append(hits)
+    while per_bin and qa.nbytes + sum(len(h) for h in per_bin) * len(HIT_COLUMNS) * 8 > DUMP_BYTES_MAX:
+        per_bin.pop()
+    hits = np.array([r for h in per_bin for r in h], dtype=np.float64).reshape(-1, len(HIT_COLUMNS))
+    np.save(os.path.join(dump_dir, "qa.npy"), qa)
+    np.save(os.path.join(dump_dir, "hits.npy"), hits)
 
 
 class Env(object):
@@ -1102,7 +1147,7 @@ def child_leg(argv, timeout_s=900):
 
 def bench_cfg3(args, env):
     """configs[2] (N = 1) / configs[3] (N > 1, strong scaling): the lineage_wf marker path over --bins-total bins from files; the
-    product shards the bins over the ranks."""
+    product shards the bins over the ranks.  --warmup untimed steps, --steps timed ones; --full adds the side measurements."""
     rank, world, workdir = env.rank, env.world, env.workdir
     nbins = args.bins_total
     emu = None
@@ -1117,45 +1162,42 @@ def bench_cfg3(args, env):
     if emu:
         os.environ["CKM_EMULATE_RANK"] = "%d/%d" % emu            # checkm_amd/dist.py: the product shards as rank r of w, no process group
     share = world if not emu else emu[1]
-    # the first pass of the process, on a slice of the bins: contexts, the 2000-profile database, device tables and workspace at working size
+    out_dir = os.path.join(workdir, "cfg3_out")
+    # the first pass of the process, on a slice of the bins (contexts, the 2000-profile database, device tables and workspace at working
+    # size), timed on its own: with --full, and whenever no warmup step would take that cost out of the timed steps
     warm = min(nbins, 128 * share)
-    t0 = time.perf_counter()
-    if os.environ.get("CKM_BENCH_SKIP_WARM") != "1":           # (counter passes of tools/gpu_collect.sh want exactly one step's launches)
+    first_pass_s = second_pass_s = None
+    if (args.full or args.warmup == 0) and os.environ.get("CKM_BENCH_SKIP_WARM") != "1":     # (counter passes of tools/gpu_collect.sh want exactly one step's launches)
+        t0 = time.perf_counter()
         lineage_pass(w, binIds[:warm], files[:warm], lin, os.path.join(workdir, "cfg3_warm"), rank)
-    env.sync()
-    first_pass_s = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    for k in range(max(0, args.warmup - 1) if warm == nbins else min(1, max(0, args.warmup - 1))):
-        lineage_pass(w, binIds[:warm], files[:warm], lin, os.path.join(workdir, "cfg3_warm"), rank)
-    env.sync()
-    second_pass_s = time.perf_counter() - t0
-    est = (second_pass_s if second_pass_s > 0 else first_pass_s) * nbins / float(warm)
-    # warmup steps proper: whole steps (all the bins), untimed -- the first one at full size still grows tables and the workspace
-    # (first_full_step_s on the line); at most two, however many were asked for, so that the run stays within minutes
-    full_warm = 0 if (warm == nbins or os.environ.get("CKM_BENCH_SKIP_WARM") == "1") else min(args.warmup, 2)
+        env.sync()
+        first_pass_s = time.perf_counter() - t0
+        if args.warmup > 1 and warm < nbins:
+            t0 = time.perf_counter()
+            lineage_pass(w, binIds[:warm], files[:warm], lin, os.path.join(workdir, "cfg3_warm"), rank)
+            env.sync()
+            second_pass_s = time.perf_counter() - t0
+    # warmup steps proper: whole steps (all the bins), untimed -- the first one still grows tables and the workspace
     full_warm_walls = []
-    for k in range(full_warm):
+    for k in range(args.warmup):
         ts = time.perf_counter()
-        lineage_pass(w, binIds, files, lin, os.path.join(workdir, "cfg3_out"), rank)
+        lineage_pass(w, binIds, files, lin, out_dir, rank)
         env.sync()
         full_warm_walls.append(time.perf_counter() - ts)
-    if full_warm_walls:
-        est = full_warm_walls[-1]
-    est = env.all_max(est)                  # (every rank must run the same number of steps: each one holds a collective)
-    steps = int(max(1, min(args.steps, args.budget_seconds // max(est, 1e-3))))
+    steps = max(1, args.steps)
     prof = None
     if args.host_profile and rank == 0:
         import cProfile
         prof = cProfile.Profile()
     env.sync()
-    sampler = ClockSampler(env.dev_index).start() if rank == 0 else None
+    sampler = ClockSampler(env.dev_index).start() if (args.full and rank == 0) else None
     t0 = time.perf_counter()
     if prof is not None:
         prof.enable()
     step_walls = []
     for k in range(steps):
         ts = time.perf_counter()
-        parts, tot = lineage_pass(w, binIds, files, lin, os.path.join(workdir, "cfg3_out"), rank)
+        parts, tot = lineage_pass(w, binIds, files, lin, out_dir, rank)
         step_walls.append(time.perf_counter() - ts)
     from checkm_amd import markerGeneFinder as _mgf
     tj = time.perf_counter()
@@ -1180,6 +1222,40 @@ def bench_cfg3(args, env):
     ssv_ms = env.all_max(tot.get("ms_ssv", 0.0))
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w, out_dir, binIds)
+    out = {"metric": "bins/hour (lineage_wf-equiv marker path: tree pass + analyze pass + qa, from genes.faa files) + residues*HMMs/s",
+           "value": nbins / per_step * 3600.0, "unit": "bins/hour", "n_gpus": world, "steps": steps, "steps_requested": args.steps, "warmup": args.warmup,
+           "ms_per_step": per_step * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+           "dtype": "f16/i16 (SSV/MSV bytes held exactly, Viterbi words) + f32 (Forward/Backward)", "data": "synthetic",
+           "config": {"workload": "configs[%d]: full lineage_wf marker DB (2000 synthetic profiles = checkm.hmm, + 43 = phylo.hmm) x %d bins of U[1500,6000] ORFs; tree pass "
+                                  "(43 models, every bin) + analyze pass (per-bin model subsets from a Lineage marker file: marker genes of the bin's lineage chain + clan "
+                                  "expansion, 300-1500 models) + qa table, through MarkerGeneFinder.find x2 -> ResultsParser.analyseResults -> printSummary (main.py:969-982)"
+                                  % (2 if world == 1 else 3, nbins),
+                      "bins_total": nbins, "parallelism": "bins sharded over %d GPU(s) by MarkerGeneFinder.find (file size x models); 1 all_gather of QA rows" % world,
+                      "steps_note": "one step = all %d bins; %d untimed warmup step(s), then %d timed step(s)" % (nbins, args.warmup, steps)},
+           "residue_hmm_per_s": residue_hmm / per_step, "residue_hmm_per_step": residue_hmm,
+           "summary": None,          # (--full: filled at the end, placed early: the side legs' headline figures survive a truncated tail of this line)
+           "parts_s_rank0": parts, "step_walls_s_rank0": step_walls, "last_release_wait_s": last_release_s, "warmup_full_steps_s_rank0": full_warm_walls,
+           "stage_pairs": stage_pairs(tot), "ssv_ms_max_rank": ssv_ms,
+           "gpu_host_split_s_rank0": {"ssv_kernels": tot.get("ms_ssv", 0.0) / 1e3, "search_calls_sum": tot.get("ms_total", 0.0) / 1e3,
+                                      "ingest": tot.get("ingest_s", 0.0), "search": tot.get("search_s", 0.0), "write": tot.get("write_s", 0.0),
+                                      "tree_find": parts["tree_find_s"], "analyze_find": parts["analyze_find_s"], "qa": parts["qa_s"],
+                                      "note": "ingest/search/write are summed over the two scan lanes (they overlap in time); tree_find + analyze_find + qa = the step"},
+           "searches_rank0": int(tot.get("searches", 0)), "cascade_fallback_lanes_rank0": int(tot.get("cascade_fallback_lanes", 0)),
+           "workspace_rank0": {"allocated_bytes_max": int(tot.get("ws_cap_bytes", 0)), "high_water_bytes_max": int(tot.get("ws_used_bytes", 0)),
+                               "note": "per context (find() keeps two on the device, each with a workspace of its own): the largest workspace a context held and the most a "
+                                       "single search asked of it, over the searches of the last timed step.  Rounds 3-4 printed the tree pass's and the analyze pass's maxima "
+                                       "ADDED UP under these names (131.7 / 63.2 GB in round 4's early runs were 65.8 + 65.8 and 15.2 + 48.0)"},
+           "setup_s": {"world_and_files": t_setup}, "full": bool(args.full)}
+    if emu:
+        out["emulated_rank"] = "%d/%d" % emu
+        out["metric"] += " -- EMULATION of rank %d of %d on one GPU (shard of the bins, all-bins host work, no collective)" % emu
+    if not args.full:
+        return out
+    out.update({"first_pass_s": first_pass_s, "first_pass_bins": warm, "second_pass_s_same_bins": second_pass_s,
+                "first_pass_overhead_s": (first_pass_s - second_pass_s) if (first_pass_s is not None and second_pass_s is not None) else None,
+                "device_state_timed_region": device_state})
     roof, _valu = ssv_roofline(tot, tot.get("ms_ssv", 0.0), -1, -1, "; cfg3: summed over the %d ckm_search calls of rank 0's batches in one step" % tot.get("searches", 0))
     roof["launches_per_step"] = int(tot.get("ssv_launches", 0))
     valu = step_util = None
@@ -1204,37 +1280,11 @@ def bench_cfg3(args, env):
                      "valu_frac_of_nominal_issue": min(1.0, NOMINAL_CYCLES_PER_INST / cyc),
                      "hbm_bytes_per_step": cnt["all_hbm_bytes"], "hbm_frac": cnt["all_hbm_bytes"] / per_step / 1e9 / HBM_PEAK_GBS,
                      "source": cnt["source"] + " (all kernels of the recorded counter passes, scaled by algorithmic bytes) over this run's ms_per_step"}
-    out = {"metric": "bins/hour (lineage_wf-equiv marker path: tree pass + analyze pass + qa, from genes.faa files) + residues*HMMs/s",
-           "value": nbins / per_step * 3600.0, "unit": "bins/hour", "n_gpus": world, "steps": steps, "steps_requested": args.steps, "warmup": args.warmup,
-           "ms_per_step": per_step * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-           "dtype": "f16/i16 (SSV/MSV bytes held exactly, Viterbi words) + f32 (Forward/Backward)", "data": "synthetic",
-           "config": {"workload": "configs[%d]: full lineage_wf marker DB (2000 synthetic profiles = checkm.hmm, + 43 = phylo.hmm) x %d bins of U[1500,6000] ORFs; tree pass "
-                                  "(43 models, every bin) + analyze pass (per-bin model subsets from a Lineage marker file: marker genes of the bin's lineage chain + clan "
-                                  "expansion, 300-1500 models) + qa table, through MarkerGeneFinder.find x2 -> ResultsParser.analyseResults -> printSummary (main.py:969-982)"
-                                  % (2 if world == 1 else 3, nbins),
-                      "bins_total": nbins, "parallelism": "bins sharded over %d GPU(s) by MarkerGeneFinder.find (file size x models); 1 all_gather of QA rows" % world,
-                      "steps_note": "one step = all %d bins; %d step(s) fit the %.0f s budget of the timed region (estimated %.1f s per step from the warm pass)" % (nbins, steps, args.budget_seconds, est)},
-           "residue_hmm_per_s": residue_hmm / per_step, "residue_hmm_per_step": residue_hmm,
-           "summary": None,          # (filled at the end, placed early: the side legs' headline figures survive a truncated tail of this line)
-           "first_pass_s": first_pass_s, "first_pass_bins": warm, "second_pass_s_same_bins": second_pass_s if second_pass_s > 0 else None,
-           "first_pass_overhead_s": (first_pass_s - second_pass_s) if second_pass_s > 0 else None,
-           "parts_s_rank0": parts, "step_walls_s_rank0": step_walls, "last_release_wait_s": last_release_s, "warmup_full_steps_s_rank0": full_warm_walls, "roofline": roof, "roofline_valu": valu, "step_utilisation": step_util, "stage_pairs": stage_pairs(tot), "ssv_ms_max_rank": ssv_ms,
-           "gpu_host_split_s_rank0": {"ssv_kernels": tot.get("ms_ssv", 0.0) / 1e3, "search_calls_sum": tot.get("ms_total", 0.0) / 1e3,
-                                      "ingest": tot.get("ingest_s", 0.0), "search": tot.get("search_s", 0.0), "write": tot.get("write_s", 0.0),
-                                      "tree_find": parts["tree_find_s"], "analyze_find": parts["analyze_find_s"], "qa": parts["qa_s"],
-                                      "note": "ingest/search/write are summed over the two scan lanes (they overlap in time); tree_find + analyze_find + qa = the step"},
-           "searches_rank0": int(tot.get("searches", 0)), "cascade_fallback_lanes_rank0": int(tot.get("cascade_fallback_lanes", 0)),
-           "workspace_rank0": {"allocated_bytes_max": int(tot.get("ws_cap_bytes", 0)), "high_water_bytes_max": int(tot.get("ws_used_bytes", 0)),
-                               "note": "per context (find() keeps two on the device, each with a workspace of its own): the largest workspace a context held and the most a "
-                                       "single search asked of it, over the searches of the last timed step.  Rounds 3-4 printed the tree pass's and the analyze pass's maxima "
-                                       "ADDED UP under these names (131.7 / 63.2 GB in round 4's early runs were 65.8 + 65.8 and 15.2 + 48.0)"},
-           "device_state_timed_region": device_state, "setup_s": {"world_and_files": t_setup}}
+    out.update({"roofline": roof, "roofline_valu": valu, "step_utilisation": step_util})
     if emu:
-        out["emulated_rank"] = "%d/%d" % emu
-        out["metric"] += " -- EMULATION of rank %d of %d on one GPU (shard of the bins, all-bins host work, no collective)" % emu
         return out
     if world == 1 and args.verify > 0 and not args.no_verify:
-        out["verify"] = verify_tables(os.path.join(workdir, "cfg3_out"), DefaultValues_HMMER_TABLE_OUT(), w.checkm_hmm, lin, binIds, files, args.verify, True, workdir)
+        out["verify"] = verify_tables(out_dir, DefaultValues_HMMER_TABLE_OUT(), w.checkm_hmm, lin, binIds, files, args.verify, True, workdir)
     else:
         out["verify"] = None
     if world == 1:

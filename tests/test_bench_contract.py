@@ -1,6 +1,7 @@
-"""The bench line's contract, checked without a GPU: the flags the driver passes parse, and the line recorded by the round's driver-shaped
-run (profiles/r06A_bench_driver_shaped_line.json = `python bench.py --gpus 1 --steps 20 --warmup 5` on one MI355X) carries every field the contract
-names, with figures that agree with each other."""
+"""The bench line's contract, checked without a GPU: the flags the driver passes parse, the line recorded by the round's driver-shaped
+run (profiles/r06A_bench_driver_shaped_line.json = `python bench.py --gpus 1 --steps 20 --warmup 5` on one MI355X, from before the side
+measurements moved behind --full: a --full line carries the same fields) carries every field the contract names, with figures that agree
+with each other, and --dump-outputs turns the files of a step into arrays."""
 import json
 import os
 import subprocess
@@ -12,7 +13,8 @@ LINE = os.path.join(ROOT, "profiles", "r06A_bench_driver_shaped_line.json")
 
 def test_driver_flags_parse():
     for args in (["--gpus", "1", "--steps", "20", "--warmup", "5"], ["--config", "genes", "--no-cpu-baseline"], ["--config", "cfg5"],
-                 ["--emulate-rank", "3/8", "--no-genes", "--no-verify"]):
+                 ["--emulate-rank", "3/8", "--no-genes", "--no-verify"], ["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
+                 ["--steps", "2", "--warmup", "1", "--dump-outputs", "out"]):
         out = subprocess.run([sys.executable, "-c", "import sys; sys.argv = ['bench.py'] + %r; import bench; a = bench.parse(); print(a.gpus, a.steps, a.warmup, a.config)" % (args,)],
                              capture_output=True, text=True, cwd=ROOT, timeout=120)
         assert out.returncode == 0, out.stderr[-1500:]
@@ -61,3 +63,36 @@ def test_recorded_line_meets_the_contract():
     assert abs(ff["seconds_per_1000_bins"] - ff["seconds"] / ff["bins"] * 1000) < 1e-6 and ff["parts_s"]["total_s"] <= ff["seconds"]
     w = d["workspace_rank0"]
     assert w["high_water_bytes_max"] <= w["allocated_bytes_max"] <= 1.3 * w["high_water_bytes_max"]
+
+
+def test_dump_outputs_reads_the_written_tables(tmp_path):
+    """bench.dump_outputs on a hand-written output directory of two bins: the QA table in bin order, every domtblout row of both passes
+    with its names turned into numbers, float64."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class P(object):
+        def __init__(self, name):
+            self.name = name
+
+    class W(object):
+        profs = [P("fam_20000"), P("fam_20001")]
+        phylo = [P("synth_PF00687")]
+    out = tmp_path / "out"
+    tree = "c000001_7  -  300 synth_PF00687  PF00687.1  220  1e-300  900.0  0.1  1  2  3.4e-33  2.1e-30  104.5  0.1  2  178  5  181  3  183 0.97 -\n"
+    analyze = "c000012_3  -  250 fam_20001  PF20001.1  180  1.2e-30  105.3  0.1  1  1  3.4e-33  2.1e-30  104.5  0.1  2  178  5  181  3  183 0.97 # 1 # 2 # 1\n"
+    for b in ("bin_0000", "bin_0001"):
+        (out / "bins" / b).mkdir(parents=True)
+        (out / "bins" / b / "hmmer.tree.txt").write_text("# target name\n" + tree + "#\n")
+        (out / "bins" / b / "hmmer.analyze.txt").write_text("# target name\n" + analyze * 2 + "#\n")
+    (out / "qa_table.tsv").write_text("Bin Id\tMarker lineage\t# genomes\t# markers\t# marker sets\t0\t1\t2\t3\t4\t5+\tCompleteness\tContamination\tStrain heterogeneity\n"
+                                      "bin_0001\tk__X (UID1)\t10\t300\t100\t5\t290\t5\t0\t0\t0\t98.50\t1.20\t0.00\n"
+                                      "bin_0000\tk__X (UID1)\t10\t300\t100\t5\t290\t5\t0\t0\t0\t97.50\t1.10\t50.00\n")
+    bench.dump_outputs(str(tmp_path / "dump"), W(), str(out), ["bin_0000", "bin_0001"])
+    qa, hits = np.load(tmp_path / "dump" / "qa.npy"), np.load(tmp_path / "dump" / "hits.npy")
+    assert qa.dtype == hits.dtype == np.float64 and qa.shape == (2, 13) and hits.shape == (6, len(bench.HIT_COLUMNS))
+    assert qa[:, 0].tolist() == [0, 1] and qa[:, -3:].tolist() == [[97.5, 1.1, 50.0], [98.5, 1.2, 0.0]]
+    row = dict(zip(bench.HIT_COLUMNS, hits[0]))
+    assert (row["bin"], row["table"], row["contig"], row["orf"], row["model"]) == (0, 0, 1, 7, 2) and row["full_evalue"] == 1e-300 and row["acc"] == 0.97
+    assert hits[:, :5].tolist() == [[b, t, c, o, m] for b in (0, 1) for t, c, o, m in ((0, 1, 7, 2), (1, 12, 3, 1), (1, 12, 3, 1))]

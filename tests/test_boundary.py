@@ -58,14 +58,26 @@ def test_bad_arguments_return_codes():
     assert b"NULL" in lib.ckm_last_error()
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/checkm"), reason="the reference package is only present in the build container")
 def test_dropin_rebinds_the_reference_classes(tmp_path):
-    """INTEGRATION.md option A, in a subprocess so the reference package never enters this test process."""
+    """INTEGRATION.md option A, in a subprocess so that no `checkm` package enters this test process.  The package is a stand-in written
+    here: the reference's modules that dropin.py touches, each with the top-level classes the reference defines in it
+    (tests/golden/reference_module_classes.json); install() must rebind the stage classes and add no name the reference lacks."""
+    import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    code = ("import checkm_amd.dropin as d; d.install()\n"
-            "import checkm.markerGeneFinder as a, checkm.resultsParser as b, checkm.markerSets as c, checkm.hmmerAligner as e, checkm.aminoAcidIdentity as f, checkm.hmmerModelParser as g\n"
+    gold = json.load(open(os.path.join(root, "tests", "golden", "reference_module_classes.json")))["classes"]
+    pkg = tmp_path / "stand_in" / "checkm"
+    pkg.mkdir(parents=True)
+    (pkg / "__init__.py").write_text("")
+    for mod, classes in gold.items():
+        (pkg / (mod.split(".")[1] + ".py")).write_text("".join("class %s(object):\n    pass\n\n\n" % c for c in classes))
+    code = ("import checkm.markerGeneFinder as a, checkm.resultsParser as b, checkm.markerSets as c, checkm.hmmerAligner as e, checkm.aminoAcidIdentity as f, checkm.hmmerModelParser as g\n"
+            "import checkm.prodigal as pr\n"
+            "classes = lambda: {m.__name__: sorted(n for n in dir(m) if isinstance(getattr(m, n), type)) for m in (a, b, c, e, f, g, pr)}\n"
+            "before = classes()\n"
+            "import checkm_amd.dropin as d; d.install()\n"
+            "assert classes() == before, (before, classes())\n"
             "mods = [a.MarkerGeneFinder.__module__, b.ResultsParser.__module__, b.ResultsManager.__module__, c.MarkerSet.__module__, c.MarkerSetParser.__module__,\n"
             "        e.HmmerAligner.__module__, f.AminoAcidIdentity.__module__]\n"
             "assert all(m.startswith('checkm_amd.') for m in mods), mods\n"
@@ -75,10 +87,9 @@ def test_dropin_rebinds_the_reference_classes(tmp_path):
             "import shutil\n"
             "gc = h.gene_caller()            # nucleotide bins: the device gene finder when no prodigal binary exists, else the mirror of ProdigalRunner\n"
             "assert gc == 'device' if shutil.which('prodigal') is None else gc.__module__ == 'checkm_amd.prodigal'\n"
-            "import checkm.prodigal as pr\n"
             "assert pr.ProdigalRunner.__module__ == 'checkm_amd.prodigal'\n"
             "print('ok')\n")
-    env = dict(os.environ, PYTHONPATH="/root/reference" + os.pathsep + root, CHECKM_DATA_PATH=str(tmp_path), PYTHONDONTWRITEBYTECODE="1")
+    env = dict(os.environ, PYTHONPATH=str(tmp_path / "stand_in") + os.pathsep + root, CHECKM_DATA_PATH=str(tmp_path), PYTHONDONTWRITEBYTECODE="1")
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-1500:]
 

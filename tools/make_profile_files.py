@@ -79,7 +79,7 @@ def one(tag):
         tot = sum(v[1] for v in fam.values())
         line = last_json(os.path.join(src, "stats3.json"))
         with open(dst("cfg3_kernel_stats.txt"), "w") as f:
-            f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --config cfg3 --bins-total %d --steps 1 --warmup 1 --no-cpu-baseline --no-cfg2 --no-emulation --no-verify (MI355X)\n"
+            f.write("# rocprofv3 --kernel-trace --stats -- python bench.py --config cfg3 --full --bins-total %d --steps 1 --warmup 1 --no-cpu-baseline --no-cfg2 --no-emulation --no-verify (MI355X)\n"
                     "# = the warm pass over 128 bins + ONE timed step (bench line of this run: %.0f ms per step, SSV launches %.0f ms by HIP events).\n"
                     "# Kernels of the two scan lanes and of the chain streams overlap in time: durations SUM to more than the wall time.\n"
                     % (line["config"]["bins_total"], line["ms_per_step"], line["roofline"]["ms_per_step_kernel"]))
@@ -93,7 +93,7 @@ def one(tag):
         line3 = last_json(os.path.join(src, "pmc3_sq.json"))
         nb3 = int(line3["config"].get("bins_total", 48))
         pmc_files(src, dst, "pmc3_", "cfg3_", line3,
-                  "CKM_BENCH_SKIP_WARM=1 python bench.py --config cfg3 --bins-total %d --steps 1 --warmup 0 --no-cpu-baseline --no-cfg2 --no-emulation --no-verify   (%d of the 1000 bins of configs[2], default batching)" % (nb3, nb3))
+                  "CKM_BENCH_SKIP_WARM=1 python bench.py --config cfg3 --full --bins-total %d --steps 1 --warmup 0 --no-cpu-baseline --no-cfg2 --no-emulation --no-verify   (%d of the 1000 bins of configs[2], default batching)" % (nb3, nb3))
     if os.path.exists(os.path.join(src, "pmc_sq.json")):
         pmc_files(src, dst, "pmc_", "", last_json(os.path.join(src, "pmc_sq.json")),
                   "CKM_BENCH_STEADY=0 CKM_BENCH_FROM_HOST=0 python bench.py --config cfg2 --steps 1 --warmup 0 --no-cpu-baseline --no-verify")
