@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcheckm_hip.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class CkmError(RuntimeError):
@@ -101,6 +101,17 @@ class NucBatchView(C.Structure):
                 ("bin_bases", C.POINTER(C.c_uint64)), ("ncontigs", C.c_uint32), ("nbins", C.c_uint32)]
 
 
+class NucSeqView(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("text_bytes", C.c_uint64), ("seq_off", C.POINTER(C.c_uint64)), ("seq_bytes", C.POINTER(C.c_uint64)),
+                ("file_first", C.POINTER(C.c_uint32)), ("seq_ids", C.POINTER(C.c_char_p)), ("nseq", C.c_uint32), ("nfiles", C.c_uint32)]
+
+
+class NucStatsColumns(C.Structure):
+    _fields_ = [("nseq", C.c_uint32), ("count", C.POINTER(C.c_uint64)), ("piece_off", C.POINTER(C.c_uint64)), ("piece_len", C.POINTER(C.c_uint64)),
+                ("tetra", C.POINTER(C.c_uint32)), ("bytes", C.c_uint64), ("tiles", C.c_uint64), ("run_starts", C.c_uint64),
+                ("ms_upload", C.c_double), ("ms_count", C.c_double), ("ms_fill", C.c_double), ("ms_total", C.c_double)]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -128,6 +139,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_align", "ckm_tables_read", "ckm_tables_assign_models", "ckm_tables_get", "ckm_tables_free",
            "ckm_orf_scan", "ckm_orf_columns_get", "ckm_orf_free", "ckm_debug_orf_flags", "ckm_genes_call", "ckm_genes_columns_get", "ckm_genes_free", "ckm_genes_coding_union", "ckm_genes_write_bin",
            "ckm_nuc_batch_read", "ckm_nuc_batch_view_get", "ckm_nuc_batch_free",
+           "ckm_nucseq_read", "ckm_nucseq_view_get", "ckm_nucseq_free", "ckm_nucstats_run", "ckm_nucstats_columns_get", "ckm_nucstats_free", "ckm_bin_genes_read",
            "ckm_debug_stages", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -196,6 +208,15 @@ def load():
     L.ckm_nuc_batch_view_get.argtypes = [C.c_void_p, C.POINTER(NucBatchView)]
     L.ckm_nuc_batch_free.argtypes = [C.c_void_p]
     L.ckm_nuc_batch_free.restype = None
+    L.ckm_nucseq_read.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ckm_nucseq_view_get.argtypes = [C.c_void_p, C.POINTER(NucSeqView)]
+    L.ckm_nucseq_free.argtypes = [C.c_void_p]
+    L.ckm_nucseq_free.restype = None
+    L.ckm_nucstats_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ckm_nucstats_columns_get.argtypes = [C.c_void_p, C.POINTER(NucStatsColumns)]
+    L.ckm_nucstats_free.argtypes = [C.c_void_p]
+    L.ckm_nucstats_free.restype = None
+    L.ckm_bin_genes_read.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -655,3 +676,74 @@ def debug_orf_flags(ctx, nbytes, reps=10):
     ms = C.c_double()
     _chk(load().ckm_debug_orf_flags(ctx.h, int(nbytes), int(reps), C.byref(ms)))
     return ms.value
+
+
+class NucSeqs(object):
+    """Nucleotide FASTA files read with the rules of CheckM's readFasta (ckm_nucseq_read, checkm/util/seqUtils.py:180-211), on the
+    library's host threads; the batch stays in the library until close()."""
+
+    def __init__(self, paths):
+        arr = (C.c_char_p * max(1, len(paths)))(*[os.fsencode(p) for p in paths])
+        self.h = C.c_void_p()
+        _chk(load().ckm_nucseq_read(arr, len(paths), C.byref(self.h)))
+        v = NucSeqView()
+        _chk(load().ckm_nucseq_view_get(self.h, C.byref(v)))
+        self.nseq, self.nfiles = int(v.nseq), int(v.nfiles)
+        arr = np.ctypeslib.as_array
+        self.seq_off = arr(v.seq_off, shape=(self.nseq,)).copy() if self.nseq else np.zeros(0, dtype=np.uint64)
+        self.seq_bytes = arr(v.seq_bytes, shape=(self.nseq,)).copy() if self.nseq else np.zeros(0, dtype=np.uint64)
+        self.file_first = arr(v.file_first, shape=(self.nfiles + 1,)).copy()
+        self._view = v
+
+    def ids(self, f=None):
+        """Sequence ids (str) of file f, or of the whole batch, in the reference's dict order."""
+        a, z = (0, self.nseq) if f is None else (int(self.file_first[f]), int(self.file_first[f + 1]))
+        return [self._view.seq_ids[i].decode("utf-8") for i in range(a, z)]
+
+    def seq(self, i):
+        """Sequence i as bytes (UTF-8)."""
+        return C.string_at(self._view.text + int(self.seq_off[i]), int(self.seq_bytes[i]))
+
+    def close(self):
+        if self.h:
+            load().ckm_nucseq_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def nucstats(ctx, seqs, tetra=False, tile_bytes=0):
+    """The device pass over a NucSeqs batch (ckm_nucstats_run).  Returns a dict: count [nseq, 8] uint64 (A, C, G, T+U, N, n, code
+    points, code points other than N), piece_off [nseq + 1], piece_len, tetra [nseq, 136] uint32 or None, and the timings."""
+    h = C.c_void_p()
+    _chk(load().ckm_nucstats_run(ctx.h, seqs.h, 1 if tetra else 0, int(tile_bytes), C.byref(h)))
+    try:
+        c = NucStatsColumns()
+        _chk(load().ckm_nucstats_columns_get(h, C.byref(c)))
+        n = int(c.nseq)
+        arr = np.ctypeslib.as_array
+        npieces = int(c.piece_off[n]) if n else 0
+        out = dict(count=arr(c.count, shape=(n, 8)).copy() if n else np.zeros((0, 8), dtype=np.uint64),
+                   piece_off=arr(c.piece_off, shape=(n + 1,)).copy(),
+                   piece_len=arr(c.piece_len, shape=(npieces,)).copy() if npieces else np.zeros(0, dtype=np.uint64),
+                   tetra=(arr(c.tetra, shape=(n, 136)).copy() if n else np.zeros((0, 136), dtype=np.uint32)) if tetra else None,
+                   bytes=int(c.bytes), tiles=int(c.tiles), run_starts=int(c.run_starts),
+                   ms_upload=c.ms_upload, ms_count=c.ms_count, ms_fill=c.ms_fill, ms_total=c.ms_total)
+    finally:
+        load().ckm_nucstats_free(h)
+    return out
+
+
+def bin_genes(seqs, gff_paths, faa_paths):
+    """(coding bases, translation table or None, gene count) per file of the batch, (-1, -1, -1) without a GFF (ckm_bin_genes_read)."""
+    n = seqs.nfiles
+    g = (C.c_char_p * max(1, n))(*[os.fsencode(p) for p in gff_paths])
+    a = (C.c_char_p * max(1, n))(*[os.fsencode(p) for p in faa_paths])
+    coding, ngenes = np.zeros(max(1, n), dtype=np.int64), np.zeros(max(1, n), dtype=np.int64)
+    table = np.zeros(max(1, n), dtype=np.int32)
+    _chk(load().ckm_bin_genes_read(g, a, seqs.h, coding.ctypes.data, table.ctypes.data, ngenes.ctypes.data))
+    return [(int(coding[k]), None if table[k] == -2 ** 31 else int(table[k]), int(ngenes[k])) for k in range(n)]

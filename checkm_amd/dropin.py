@@ -30,3 +30,19 @@ def install():
     from checkm_amd import prodigal as pr
     checkm.prodigal.ProdigalRunner = pr.ProdigalRunner
     checkm.prodigal.ProdigalGeneFeatureParser = pr.ProdigalGeneFeatureParser
+    # bin statistics (tree and analyze step: storage/bin_stats.*.tsv) and `checkm tetra`: the nucleotide pass on the device.  Guarded: a
+    # CheckM package without these modules keeps what it has.
+    try:
+        import checkm.binStatistics
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import binStatistics as bs
+        checkm.binStatistics.BinStatistics = bs.BinStatistics
+    try:
+        import checkm.genomicSignatures
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import genomicSignatures as gs
+        checkm.genomicSignatures.GenomicSignatures = gs.GenomicSignatures

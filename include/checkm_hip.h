@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 7
+#define CKM_ABI_VERSION 8
 
 enum {
   CKM_OK      =  0,
@@ -356,6 +356,54 @@ typedef struct {
 int  ckm_nuc_batch_read(const char *const *paths, uint32_t nbins, ckm_nuc_batch **out);
 int  ckm_nuc_batch_view_get(const ckm_nuc_batch *b, ckm_nuc_batch_view *out);
 void ckm_nuc_batch_free(ckm_nuc_batch *b);
+
+/* ---- bin statistics and tetranucleotide signatures (ABI 8) -----------------------------------------------------------------------------
+ * ckm_nucseq_read replaces checkm/util/seqUtils.py:180-211 (readFasta) as BinStatistics._processBin (checkm/binStatistics.py:100-101) and
+ * GenomicSignatures.calculate (checkm/genomicSignatures.py:157) call it, rule for rule: the file is read as UTF-8 text (invalid UTF-8 is
+ * CKM_EFORMAT, as the reference fails on it), '.gz' names through zlib; "\n", "\r\n" and a lone "\r" end a line; a line of white space
+ * only is skipped; a header's id is its first white-space delimited word; every other line loses exactly its last character
+ * (line[0:-1]: the line end, or the last character of a file that does not end in one) and keeps blanks and tabs; a repeated id keeps
+ * its first place and takes the later record's sequence.  Host threads, a file per thread.  ckm_nuc_batch_read is unchanged: its rules
+ * are the gene caller's.  The view lives until ckm_nucseq_free; sequence s = text[seq_off[s] .. seq_off[s] + seq_bytes[s]) (UTF-8
+ * bytes, 16-byte aligned), file f owns sequences file_first[f] .. file_first[f+1]-1 in the reference's dict order. */
+typedef struct ckm_nucseq ckm_nucseq;
+typedef struct {
+  const char        *text;
+  uint64_t           text_bytes;
+  const uint64_t    *seq_off, *seq_bytes;   /* [nseq] */
+  const uint32_t    *file_first;            /* [nfiles + 1] */
+  const char *const *seq_ids;               /* [nseq] */
+  uint32_t           nseq, nfiles;
+} ckm_nucseq_view;
+int  ckm_nucseq_read(const char *const *paths, uint32_t nfiles, ckm_nucseq **out);
+int  ckm_nucseq_view_get(const ckm_nucseq *b, ckm_nucseq_view *out);
+void ckm_nucseq_free(ckm_nucseq *b);
+
+/* The device pass over a batch: replaces baseCount / calculateGC / calculateSeqStats (checkm/util/seqUtils.py:279-286,
+ * checkm/binStatistics.py:173-234) and GenomicSignatures.seqSignature's counting loop (checkm/genomicSignatures.py:131-149).  Per sequence:
+ * count[s*8 + k] = A, C, G, T+U (either case), 'N', 'n', code points (len(seq)), code points other than 'N'; the contig pieces
+ * piece_len[piece_off[s] .. piece_off[s+1]) (scaffold.split('NNNNNNNNNN'), 'N' removed, empty pieces dropped); with tetra != 0 the 136
+ * canonical 4-mer counts tetra[s*136 ..] in _makeKmerColNames order (windows of four A/C/G/T bytes, either case).  tile_bytes: bytes of
+ * sequence per wavefront (0 = 4096; a multiple of 16, at most 1 MiB).  Integer results: identical from run to run. */
+typedef struct ckm_nucstats ckm_nucstats;
+typedef struct {
+  uint32_t        nseq;
+  const uint64_t *count;                    /* [nseq * 8] */
+  const uint64_t *piece_off;                /* [nseq + 1] */
+  const uint64_t *piece_len;
+  const uint32_t *tetra;                    /* [nseq * 136] or NULL */
+  uint64_t        bytes, tiles, run_starts; /* bytes uploaded, tiles, runs of >= 10 'N' */
+  double          ms_upload, ms_count, ms_fill, ms_total;   /* HIP events: upload, count pass, fill pass; wall of the call */
+} ckm_nucstats_columns;
+int  ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, uint32_t tile_bytes, ckm_nucstats **out);
+int  ckm_nucstats_columns_get(const ckm_nucstats *r, ckm_nucstats_columns *out);
+void ckm_nucstats_free(ckm_nucstats *r);
+
+/* Replaces BinStatistics.calculateCodingDensity's file reading (checkm/binStatistics.py:236-253) for every file of a batch, on host threads:
+ * gff_paths[f] / faa_paths[f] are bins/<binId>/genes.gff / genes.faa of file f.  coding[f] = bases of f's sequences inside the union of
+ * their genes (ProdigalGeneFeatureParser.codingBases summed over the ids), trans_table[f] = the first '# Model Data' line's transl_table
+ * (INT32_MIN: none), ngenes[f] = distinct records of genes.faa; all three -1 when the GFF does not exist.  No device needed. */
+int  ckm_bin_genes_read(const char *const *gff_paths, const char *const *faa_paths, const ckm_nucseq *b, int64_t *coding, int32_t *trans_table, int64_t *ngenes);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
