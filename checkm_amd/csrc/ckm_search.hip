@@ -693,9 +693,10 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   cd0.ework = dev_table<FbWork>(ctx->c_ework, cp.ework); cd0.cap_ework = cp.ework;
   cd0.rwork = dev_table<FbWork>(ctx->c_rwork, cp.rwork); cd0.ens = dev_table<EnsWork>(ctx->c_ens, cp.rwork); cd0.cap_rwork = cp.rwork;
   uint32_t *d_ensq = dev_table<uint32_t>(ctx->c_ensq, (size_t)4 * cp.rwork);       // region ids by sequence part
-  // zone 1: special rows and decoding terms of the parser items (~a few KB for ~0.3 % of the pairs); zone 2: everything else
+  // zone 1: special rows and decoding terms of the parser items (~a few KB for ~0.3 % of the pairs: 64 B per pair until a search asked
+  // for more); zone 2: everything else
   {
-    const uint64_t z1 = std::min<uint64_t>(ws_floats / 2, ((uint64_t)total_pairs * 64 + ((uint64_t)64 << 20)) / 4) & ~(uint64_t)31;
+    const uint64_t z1 = std::min<uint64_t>(ws_floats / 2, ((uint64_t)((double)total_pairs * cp.z1_per_pair) + ((uint64_t)64 << 20)) / 4) & ~(uint64_t)31;
     cd0.ws_top = d_tops; cd0.ws_cap = z1;
     cd0.ws2_top = d_tops + 2; cd0.ws2_base = z1; cd0.ws2_cap = ws_floats - z1;
   }
@@ -899,6 +900,14 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
     const uint64_t w = want + want / 4 + 16;
     if ((pairs / std::max<uint64_t>(1, (uint64_t)div * shrink) >= floor_ || shrink > 1) && !((halved >> kind) & 1u)) { div = std::max<uint32_t>(1, div / 2); halved |= 1u << kind; }
     if (shrink == 1) floor_ = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(floor_, w), 1u << 14);
+    // More than the floor may become (every group pays the floor, so it stays small): then the group's SHARE has to give it the entries,
+    // whatever the larger term was -- else max(pairs / div, floor) stays below `want` and this kind of search overflows in every call.  A
+    // group that asks for more entries than it has pairs (several envelopes or regions per pair) gets them from the floor after all.
+    if (shrink == 1 && w > (1u << 14)) {
+      const uint64_t d = pairs / w;
+      if (d >= 1) div = (uint32_t)std::min<uint64_t>(div, d);
+      else { div = 1; floor_ = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(floor_, w), 1u << 20); }
+    }
   };
   uint64_t n_cand = 0, n_nores = 0;
   for (size_t g = 0; g < NG; ++g) {
@@ -923,6 +932,14 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   st.ws_cap_bytes = ctx->ws.cap; st.ws_used_bytes = (std::min<uint64_t>(h_tops[0], cd0.ws_cap) + h_tops[2]) * 4;
   // the bump allocator counts every request, granted or not: after an overflow the search's whole demand is known, and the next one of its
   // kind gets that (+15 %) instead of a blind x1.5
+  // (zone 1 the same way, per pair: where most pairs are hits -- a small database of families that every protein carries -- 64 B per
+  //  pair is a third of the demand, and without this such a search took the host-driven cascade in every call)
+  // (never shrinks; z1 is also held to half of the workspace: where THAT is the smaller term the search asks for more than the workspace
+  //  budget gives and stays host-driven -- the trace says so)
+  if (h_tops[0] > cd0.ws_cap && tr && cd0.ws_cap == ((ws_floats / 2) & ~(uint64_t)31))
+    fprintf(stderr, "ckm-trace w%d workspace zone 1 is held to half of the workspace (%.3f GB) and this search asked for %.3f GB: it stays on the host-driven cascade\n", ctx->id,
+            (double)cd0.ws_cap * 4 / 1e9, (double)h_tops[0] * 4 / 1e9);
+  if (h_tops[0] > cd0.ws_cap) cp.z1_per_pair = std::max(cp.z1_per_pair, (float)(1.15 * (double)h_tops[0] * 4.0 / (double)std::max<uint64_t>(total_pairs, 1)));
   if (h_tops[2] > cd0.ws2_cap)
     cp.ws_per_cell = std::max(cp.ws_per_cell, (float)(1.15 * (double)(h_tops[2] + cd0.ws_cap) * 4.0 / std::max(cell_sum, 1.0)));
   if (tr) fprintf(stderr, "ckm-trace w%d workspace: %.3f GB held, %.3f GB asked for by this search (zone 1 %.3f of %.3f, zone 2 %.3f of %.3f), %.3e cells -> %.2f B per cell (estimate %.2f)\n", ctx->id,

@@ -174,6 +174,14 @@ void x_hexamer_background(GExec &e, const uint8_t *code, const uint64_t *seq_off
 // per start); stages 1 and 2: the start's current motif (nd.mot) and, in stage 1, the shorter words inside it, into
 // tab[slot][length - 3][spacer class][word].  On the device a workgroup per part with the counters in LDS.
 struct MotifPart { uint32_t lo, hi, slot, pad; };
+// Nodes per part of a bin of n nodes: an eighth of the bin in whole 256-node blocks, at most MOTIF_PART_MAX.  The device counts stages 1
+// and 2 in 16-bit halves of an LDS word, and in stage 1 ONE start can hit ONE entry four times (a 6-base motif whose four inner 3-base
+// words are equal and fall in one spacer class: a homopolymer upstream of the start), so a part may hold at most 65535 / 4 starts.
+constexpr uint32_t MOTIF_HITS_PER_START = 4, MOTIF_PART_MAX = (65535u / MOTIF_HITS_PER_START) & ~255u;                  // 16128
+inline uint32_t motif_part_nodes(uint32_t n, uint32_t part_max = MOTIF_PART_MAX) {
+  const uint32_t per = ((n + 7) / 8 + 255) & ~255u;
+  return per < 256u ? 256u : per > part_max ? part_max : per;
+}
 void x_motif_bg(GExec &e, int stage, const Nodes &nd, const int32_t *seq_len, const MotifPart *parts, uint32_t nparts, uint32_t *tab);
 
 // hexamer sums (bin tables staged in LDS on the device) and Shine-Dalgarno bins of every start node

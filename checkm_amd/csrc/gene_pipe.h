@@ -917,8 +917,8 @@ inline void gene_pipeline(GExec &e, const PipeInput &in, GeneResult &out) {
       // the rounds' background words: every bin's nodes in eight parts, a workgroup each (x_motif_bg)
       std::vector<MotifPart> h_bgp;
       for (size_t k = 0; k < nsl; ++k) {
-        // (a part holds fewer than 65536 nodes: the later rounds count in 16-bit halves)
-        const uint32_t b = ns_bins[k], lo = seq_lo[b], n = seq_n[b], per = std::min<uint32_t>(65280u, std::max<uint32_t>(256u, ((n + 7) / 8 + 255) & ~255u));
+        // (the later rounds count in 16-bit halves: motif_part_nodes keeps a part small enough for them, gene_exec.h)
+        const uint32_t b = ns_bins[k], lo = seq_lo[b], n = seq_n[b], per = motif_part_nodes(n);
         for (uint32_t a = 0; a < n; a += per) h_bgp.push_back(MotifPart{lo + a, std::min(n, a + per) + lo, (uint32_t)k, 0});
       }
       GBuf d_bgp; d_bgp.ensure(std::max<size_t>(1, h_bgp.size()) * sizeof(MotifPart));

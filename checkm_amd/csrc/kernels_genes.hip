@@ -305,7 +305,10 @@ void x_rbs(GExec &e, const uint8_t *code, const uint64_t *seq_off, const int32_t
 // A workgroup per eighth of a bin's nodes, the counters in LDS, one flush: the thread-per-node kernel sent 52 atomics per start (first
 // round) or up to seven (stage 1) to tables in memory -- 42 M + 45 M per 48-bin call, and its wavefronts stayed resident until they had
 // drained (27 % of a call's wavefront-cycles: profiles/r06o).  Stage 0: 5440 counters (64 + 256 + 1024 + 4096 words of 3 .. 6 bases).
-// Stages 1 / 2: four spacer classes of those, 21760 counters held as 16-bit halves of 10880 words (a part has fewer than 65536 starts).
+// Stages 1 / 2: four spacer classes of those, 21760 counters held as 16-bit halves of 10880 words.  A start adds at most
+// MOTIF_HITS_PER_START to one entry and a part holds at most MOTIF_PART_MAX nodes (gene_exec.h: motif_part_nodes), so no half carries
+// into its neighbour.
+static_assert(MOTIF_HITS_PER_START * MOTIF_PART_MAX <= 65535u, "a 16-bit half of motif_bg12_kernel's counters could overflow");
 constexpr int MOT_WORDS = 5440;
 __device__ __forceinline__ int mot_off(int i) { return ((64 << (2 * i)) - 64) / 3; }
 __global__ void __launch_bounds__(256) motif_bg0_kernel(Nodes nd, const int32_t *__restrict__ seq_len, const MotifPart *__restrict__ parts, uint32_t *__restrict__ bg0) {
@@ -554,8 +557,11 @@ __device__ __forceinline__ void dp_enter(const Nodes &nd, DpRing &ring, DpBlock 
     ring.cls[cls][before[cls] & (DPC - 1)] = (unsigned short)rel;
   }
   if (lane == 0) { for (int c = 0; c < 4; ++c) DP_LDS_ST(&ring_tot[c], tot[c]); }
-  // where the node's candidates begin: a forward stop / reverse start reaches back to dp_pos_floor only (the records of this block are in
-  // the ring by now -- LDS operations of one wavefront complete in order)
+  // where the node's candidates begin: a forward stop / reverse start reaches back to dp_pos_floor only.  The search below reads records
+  // that OTHER lanes of this wavefront stored just above: the hardware completes one wavefront's LDS operations in order, the fence and
+  // the barrier keep the compiler from moving the loads over the stores (neither emits an instruction).
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
   if (in) {
     int le = lo;
     if (dp_class_pos_bounded(cls) && lo >= dp_ring_lo(e0 - 2 * DPB)) {      // (the nodes are entered two blocks before they are scored: what is in the ring now is still there then)

@@ -165,3 +165,27 @@ def dp_stress_genomes():
             [base[0], base[1][:8000] + many + base[1][8000:], base[2][:5000] + rc(many) + base[2][5000:]],
             [base[2], dense + base[0][:20000] + rc(dense), base[1][:3000] + pure + base[1][3000:6000] + rc(pure) + base[1][6000:9000]],
             shorts + base[:1]]
+
+
+def genome_scale_genomes():
+    """Bins (lists of contig strings) of the size users bring, where the device's structures change regime:
+    (a) 4 Mb without Shine-Dalgarno sites (the upstream-motif training runs; about 165 000 nodes: more than eight parts of
+        motif_part_nodes' 16128, checkm_amd/csrc/gene_exec.h);
+    (b) 4 Mb with Shine-Dalgarno sites upstream of 60 % of the genes;
+    (c) the counter-saturation bin: a 4 Mb genome without Shine-Dalgarno sites that carries 36 open reading frames of 48 kb, half of them
+        reverse-complemented, each 2000 times the unit A x 21 + ATG -- 36 000 in-frame starts behind one another on either strand whose
+        18-base upstream window is poly-A, so a start's best motif is AAAAAA wherever it looks and its four inner AAA words fall into one
+        entry of the stage-1 background table.  tests/test_gene_emu.py proves from the emulation's 32-bit tables that one part of the
+        former layout (an eighth of the bin, up to 65280 nodes) counts more than 65535 in one entry here and that no bin does with
+        motif_part_nodes."""
+    from synthdata import synth_genome as sg
+    comp = {"A": "T", "C": "G", "G": "C", "T": "A"}
+
+    def rc(s):
+        return "".join(comp[c] for c in reversed(s))
+    a = [s for _c, s in sg.make_genome(900, n_contigs=10, contig_len=(380000, 420000), gc=0.45, sd_frac=0.0)]
+    b = [s for _c, s in sg.make_genome(901, n_contigs=8, contig_len=(450000, 550000), gc=0.55, sd_frac=0.6)]
+    base = [s for _c, s in sg.make_genome(902, n_contigs=10, contig_len=(380000, 420000), gc=0.4, sd_frac=0.0)]
+    fwd = (("A" * 21 + "ATG") * 2000 + "TAA") * 18
+    c = [base[0][:50000] + fwd + base[0][50000:], base[1][:30000] + rc(fwd) + base[1][30000:]] + base[2:]
+    return [a, b, c]

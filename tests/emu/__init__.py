@@ -44,12 +44,14 @@ def lib():
         L.emu_genes_error.argtypes = [C.c_void_p]
         L.emu_genes_columns.argtypes = [C.c_void_p, C.POINTER(Columns)]
         L.emu_genes_free.argtypes = [C.c_void_p]
+        L.emu_genes_bg_part_max.argtypes = [C.POINTER(C.c_uint32)]
         _lib = L
     return _lib
 
 
-def call_genes(bins, trans_table=11, mask=True):
-    """Same contract as checkm_amd._lib.call_genes: (columns, per-bin dict)."""
+def call_genes(bins, trans_table=11, mask=True, part_max=False):
+    """Same contract as checkm_amd._lib.call_genes: (columns, per-bin dict).  part_max: also keep the figures of bg_part_max() (two more
+    passes over the start nodes per training round; one call at a time)."""
     parts, bin_first = [], [0]
     for contigs in bins:
         for c in contigs:
@@ -61,6 +63,7 @@ def call_genes(bins, trans_table=11, mask=True):
     bf = np.asarray(bin_first, dtype=np.uint32)
     text = b"".join(parts)
     h = C.c_void_p()
+    lib().emu_genes_bg_part_max_enable(1 if part_max else 0)
     rc = lib().emu_genes_call(text, off.ctypes.data, len(parts), bf.ctypes.data, len(bins), int(trans_table), 1 if mask else 0, C.byref(h))
     try:
         if rc != 0:
@@ -80,3 +83,11 @@ def call_genes(bins, trans_table=11, mask=True):
     finally:
         lib().emu_genes_free(h)
     return out, per_bin
+
+
+def bg_part_max():
+    """(with the pipeline's parts, with parts capped at 65280 nodes as they once were): the largest count one part gave one entry of the
+    stage-1/2 background tables in any training round of the last call_genes(part_max=True) -- what one 16-bit half of motif_bg12_kernel has to hold."""
+    v = (C.c_uint32 * 2)()
+    lib().emu_genes_bg_part_max(v)
+    return int(v[0]), int(v[1])

@@ -178,12 +178,36 @@ void x_path_ends(GExec &, const Nodes &nd, const uint32_t *seq_lo, const uint32_
   }
 }
 
+// The largest count ONE part gives ONE stage-1/2 entry, over every round of the last call: what a workgroup of motif_bg12_kernel holds in a
+// 16-bit half.  [0]: for the parts the pipeline made (motif_part_nodes); [1]: for the layout that capped a part at 65280 nodes.
+static uint32_t g_bg_part_max[2];
+static bool g_bg_part_max_on = false;            // (emu_genes_bg_part_max_enable: only the test that asks for the figures pays for them)
+static void bg_part_max(int which, int stage, const Nodes &nd, const int32_t *seq_len, uint32_t lo, uint32_t hi, uint32_t per, std::vector<uint32_t> &t) {
+  for (uint32_t a = lo; a < hi; a += per) {
+    std::fill(t.begin(), t.end(), 0u);
+    for (uint32_t x = a; x < std::min(hi, a + per); ++x) {
+      if (nd.type[x] >= G_STOP || nd.edge[x] == 1) continue;
+      const int sl = seq_len[nd.seq[x]], strand = nd.strand[x], start = strand == 1 ? nd.ndx[x] : sl - 1 - nd.ndx[x];
+      motif_words_stage12(nd.mot[x], nd.upw[x], start, stage, [&](int i, int sp, int w) { const uint32_t v = ++t[((size_t)i * 4 + sp) * 4096 + w]; if (v > g_bg_part_max[which]) g_bg_part_max[which] = v; });
+    }
+  }
+}
 void x_motif_bg(GExec &, int stage, const Nodes &nd, const int32_t *seq_len, const MotifPart *parts, uint32_t nparts, uint32_t *tab) {
   for (uint32_t p = 0; p < nparts; ++p) for (uint32_t x = parts[p].lo; x < parts[p].hi; ++x) {
     if (nd.type[x] >= G_STOP || nd.edge[x] == 1) continue;
     const int sl = seq_len[nd.seq[x]], strand = nd.strand[x], start = strand == 1 ? nd.ndx[x] : sl - 1 - nd.ndx[x];
     if (stage == 0) motif_words_stage0(nd.upw[x], start, [&](int i, int w) { tab[((size_t)parts[p].slot * 4 + i) * 4096 + w]++; });
     else motif_words_stage12(nd.mot[x], nd.upw[x], start, stage, [&](int i, int sp, int w) { tab[(size_t)parts[p].slot * 65536 + ((size_t)i * 4 + sp) * 4096 + w]++; });
+  }
+  if (stage == 0 || !g_bg_part_max_on) return;
+  std::vector<uint32_t> t(65536);
+  for (uint32_t p = 0; p < nparts;) {                   // (a bin's parts follow one another: its node range is [first part's lo, last part's hi))
+    uint32_t q = p;
+    while (q + 1 < nparts && parts[q + 1].slot == parts[p].slot) ++q;
+    const uint32_t lo = parts[p].lo, hi = parts[q].hi, n = hi - lo;
+    for (uint32_t k = p; k <= q; ++k) bg_part_max(0, stage, nd, seq_len, parts[k].lo, parts[k].hi, parts[k].hi - parts[k].lo, t);
+    bg_part_max(1, stage, nd, seq_len, lo, hi, motif_part_nodes(n, 65280u), t);
+    p = q + 1;
   }
 }
 
@@ -236,6 +260,7 @@ extern "C" int emu_genes_call(const char *text, const uint64_t *contig_off, uint
     in.text = text; in.contig_off = contig_off; in.ncontigs = ncontigs; in.bin_first = bin_first; in.nbins = nbins; in.trans_table = trans_table; in.mask_runs = mask_runs;
     in.pfor = [](size_t n, const std::function<void(size_t)> &f) { for (size_t i = 0; i < n; ++i) f(i); };
     GExec e;
+    g_bg_part_max[0] = g_bg_part_max[1] = 0;
     gene_pipeline(e, in, o->r);
     return 0;
   } catch (const std::exception &ex) { o->err = ex.what(); return -1; }
@@ -251,4 +276,6 @@ extern "C" void emu_genes_columns(const emu_genes *gg, emu_columns *c) {
   c->nbins = g->bin_trained.size(); c->bin_trained = g->bin_trained.data(); c->bin_uses_sd = g->bin_uses_sd.data(); c->bin_gc = g->bin_gc.data();
   c->bin_bases = g->bin_bases.data(); c->bin_coding = g->bin_coding.data(); c->bin_nodes = g->bin_nodes_find.data();
 }
+extern "C" void emu_genes_bg_part_max_enable(int on) { g_bg_part_max_on = on != 0; }
+extern "C" void emu_genes_bg_part_max(uint32_t *out) { out[0] = g_bg_part_max[0]; out[1] = g_bg_part_max[1]; }
 extern "C" void emu_genes_free(emu_genes *g) { delete g; }

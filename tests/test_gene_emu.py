@@ -88,6 +88,28 @@ def test_emulated_pipeline_on_the_dynamic_programs_hard_cases():
     assert _same_as_oracle(common.dp_stress_genomes(), 11) > 100
 
 
+def test_saturation_bin_overflows_a_16_bit_half_only_under_the_former_parts():
+    """motif_bg12_kernel (checkm_amd/csrc/kernels_genes.hip) counts a part's stage-1/2 background words in 16-bit halves.  From the
+    emulation's 32-bit counts, per part: bin (c) of common.genome_scale_genomes puts more than 65535 into ONE entry of ONE part when a part is
+    an eighth of the bin up to 65280 nodes (the layout before motif_part_nodes, restated in tests/emu/gene_emu.cpp: x_motif_bg), so the GPU
+    test of that bin (tests/test_gpu_genes.py) is not vacuous; an ordinary 4 Mb bin stays below under that layout; and with the parts the
+    pipeline makes now no test bin exceeds 65535."""
+    from tests import common
+    a, b, c = common.genome_scale_genomes()
+    for table in (11, 4):
+        _cols, per_bin = emu.call_genes([c], table, part_max=True)
+        now, former = emu.bg_part_max()
+        assert int(per_bin["uses_sd"][0]) == 0 and int(per_bin["nodes"][0]) >= 8 * 17000
+        assert former > 65535, (table, former)
+        assert 0 < now <= 65535, (table, now)
+    _cols, per_bin = emu.call_genes([a], 11, part_max=True)
+    now, former = emu.bg_part_max()
+    assert int(per_bin["uses_sd"][0]) == 0 and 0 < former <= 65535 and 0 < now <= 65535, (now, former)
+    for bins in ([b], [_plain(g) for g in _genomes()], common.edge_genomes(), common.dp_stress_genomes()):
+        emu.call_genes(bins, 11, part_max=True)
+        assert emu.bg_part_max()[0] <= 65535
+
+
 def test_product_does_not_load_the_emulation():
     import os
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "checkm_amd")

@@ -36,6 +36,40 @@ def _okey(g):
 
 
 @pytest.mark.parametrize("table", [11, 4])
+def test_genome_size_bins_identical_to_the_oracle(gpu_ctx, table):
+    """Bins of 4 Mb (tests/common.py: genome_scale_genomes): more than 10^5 nodes per dynamic program, more than eight parts of the
+    motif-background counts (gene_exec.h: motif_part_nodes), and the bin that overflowed a 16-bit half of motif_bg12_kernel's counters while a
+    part could hold 65280 nodes (tests/test_gene_emu.py shows that it does) -- against the oracle, and twice in one process (the ring records of
+    dp_enter are read by other lanes than wrote them: the same columns both times)."""
+    from tests import common
+    genomes = common.genome_scale_genomes()
+    cols, per_bin, _stats = _lib.call_genes(gpu_ctx, genomes, table)
+    cols2, per_bin2, _stats2 = _lib.call_genes(gpu_ctx, genomes, table)
+    assert cols["proteins"] == cols2["proteins"]
+    for f in cols:
+        if f != "proteins":
+            assert np.array_equal(cols[f], cols2[f]), f
+    for f in ("trained", "uses_sd", "gc"):
+        assert np.array_equal(per_bin[f], per_bin2[f]), f
+    by_bin = {}
+    for k in range(len(cols["begin"])):
+        by_bin.setdefault(int(cols["bin"][k]), []).append(k)
+    for b, g in enumerate(genomes):
+        t, ogenes, oprots = og.find_genes(g, table)
+        ks = by_bin.get(b, [])
+        assert t is not None and per_bin["trained"][b] and int(per_bin["uses_sd"][b]) == t.uses_sd, b
+        assert t.uses_sd == (1 if b == 1 else 0), b                     # (a) and (c) train upstream motifs, (b) Shine-Dalgarno bins
+        assert float(per_bin["gc"][b]) == t.gc
+        assert len(ogenes) > 2500
+        assert [_key(cols, k) for k in ks] == [_okey(x) for x in ogenes], b
+        for f in ("gc_cont", "conf", "score", "cscore", "sscore", "rscore", "uscore", "tscore"):
+            got = np.asarray([cols[f][k] for k in ks], dtype=np.float64).view(np.uint64)
+            want = np.asarray([getattr(x, f) for x in ogenes], dtype=np.float64).view(np.uint64)
+            assert (got == want).all(), (b, f, np.nonzero(got != want)[0][:3])
+        assert [cols["proteins"][k] for k in ks] == oprots, b
+
+
+@pytest.mark.parametrize("table", [11, 4])
 def test_genes_identical_to_the_oracle(gpu_ctx, table):
     from tests import common
     genomes = _genomes() + [[("e%d" % k, s) for k, s in enumerate(g)] for g in common.edge_genomes()]      # + empty / tiny / all-N contigs, IUPAC, mask edges, the 20 kb limit

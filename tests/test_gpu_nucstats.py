@@ -128,3 +128,79 @@ def test_analyze_step_reuses_the_tree_step(tmp_path):
         f.write(b">extra\nACGTACGT\n")
     b2.calculate(paths, str(out), "bin_stats.analyze.tsv")
     assert b2.last_timing["reused"] == len(paths) - 1
+
+
+def seam_sequences():
+    """Sequences whose runs of 'N' begin at chosen distances in front of every boundary of the device pass: a lane's 16 bytes, a wave
+    step's 1024, the tiles' 4096 and 65536, and the end of the sequence.  Every other byte is one of ACGTacgt, up to the last one."""
+    rng = np.random.default_rng(2024)
+
+    def filler(n):
+        return bytearray(rng.choice(np.frombuffer(b"ACGTacgt", dtype=np.uint8), size=n, p=[.22, .22, .22, .22, .03, .03, .03, .03]).tobytes())
+    out = []
+    # one sequence per seam, run length and distance in front of it: the run's first byte sits at S - d
+    for S in (16, 48, 1008, 1024, 2048, 3072, 4096, 8192, 65536, 131072):
+        for L in (9, 10, 11, 25):
+            for d in range(13):
+                s = filler(S + 61 + (L + d) % 7)
+                s[S - d:S - d + L] = b"N" * L
+                out.append(bytes(s))
+    # the end of the sequence: runs that end exactly at, one before and nine before the last byte -- behind a lane, a wave-step and a tile seam
+    for n in (200, 1024 + 5, 4096 + 16, 4096 + 3, 65536 + 12):
+        for L in (9, 10, 11, 25):
+            for back in (0, 1, 9):
+                s = filler(n)
+                s[n - back - L:n - back] = b"N" * L
+                out.append(bytes(s))
+    # a sequence that ends INSIDE what would be a longer run at each seam (the bytes behind its end belong to the next sequence or the slack)
+    for S in (1024, 4096, 65536):
+        for k in (1, 5, 9, 10, 11):
+            s = filler(S)
+            s[S - k:] = b"N" * k
+            out.append(bytes(s))
+            s = filler(S + k)
+            s[S - 3:] = b"N" * (k + 3)
+            out.append(bytes(s))
+    out.append(b"N" * 10)                                     # nothing but a run
+    out.append(b"N" * 9)                                      # nothing but N, and no run
+    out.append(b"N" * 10 + bytes(filler(50)))                 # a run at offset 0
+    for S in (64, 1024, 4096):                                # the byte in front of the run is a lower-case n (not part of it), at a seam and one behind it
+        for at in (S, S + 1):
+            s = filler(S + 80)
+            s[at - 1:at] = b"n"
+            s[at:at + 10] = b"N" * 10
+            out.append(bytes(s))
+    s = filler(4096 * 3)                                      # runs that span a whole tile and two seams (4096) / many wave steps
+    s[4090:8200] = b"N" * (8200 - 4090)
+    out.append(bytes(s))
+    return out
+
+
+def test_runs_of_n_on_every_seam(tmp_path):
+    """The halo assembly of the device pass (kernels_nucstats.hip: load_lane -- lane 63's extra load, lane 0's byte in front, the cut at a
+    sequence's end) decides whether a run of ten 'N' BEGINS in a lane.  Runs of 9, 10, 11 and 25 begin 0 .. 12 bytes in front of every
+    kind of seam, and end at / one before / nine before a sequence's end; three tile sizes (the wave step, the default, 64 KiB) against the
+    numpy / regular-expression restatement and against each other."""
+    flat = seam_sequences()
+    p = write_fasta(tmp_path / "seams.fna", [("s%05d" % k, s) for k, s in enumerate(flat)])
+    seqs = _lib.NucSeqs([p])
+    assert seqs.nseq == len(flat) and all(seqs.seq(i) == flat[i] for i in range(0, len(flat), 37))
+    ctx = runtime.get_ctx()
+    counts, pieces, tetra = restated(flat)
+    assert sum(len(x) for x in pieces) > len(flat) * 3 // 2           # most sequences are cut in two
+    res = {}
+    for tile in (0, 1024, 65536):
+        r = res[tile] = _lib.nucstats(ctx, seqs, tetra=True, tile_bytes=tile)
+        assert np.array_equal(r["count"], counts), tile
+        assert np.array_equal(r["tetra"], tetra), (tile, np.nonzero((r["tetra"] != tetra).any(axis=1))[0][:5])
+        for i, want in enumerate(pieces):
+            assert list(r["piece_len"][int(r["piece_off"][i]):int(r["piece_off"][i + 1])]) == want, (tile, i, len(flat[i]))
+    assert res[0]["tiles"] > res[65536]["tiles"] and res[1024]["tiles"] > res[0]["tiles"]
+    for tile in (1024, 65536):
+        for k in ("count", "piece_off", "piece_len", "tetra"):
+            assert np.array_equal(res[0][k], res[tile][k]), (tile, k)
+    # a tile size the pass cannot take is refused with an error, not run
+    for bad in (24, (1 << 20) + 16):
+        with pytest.raises(_lib.CkmError):
+            _lib.nucstats(ctx, seqs, tetra=True, tile_bytes=bad)
+    seqs.close()

@@ -75,10 +75,11 @@ def _omodels(models):
 
 
 def verify(out_dir, table, hmm_path, bin_ids, files, models_by_bin, k_bins=3, n_models=40, seed=1, threads=None,
-           marker_sets=None, qa_rows=None, pfam_text=None, with_rows=16):
+           marker_sets=None, qa_rows=None, pfam_text=None, with_rows=16, whole_bins=()):
     """out_dir/bins/<binId>/<table> against the oracles for `k_bins` sampled bins.
     models_by_bin: what find() returned ({binId: {acc: HmmModel}}).  marker_sets ({binId: BinMarkerSets}) + qa_rows ({binId: tab-separated
-    row of printSummary format 1}) + pfam_text switch the reduce half on."""
+    row of printSummary format 1}) + pfam_text switch the reduce half on.  whole_bins: indices into bin_ids that are always among the
+    checked bins, with EVERY model of the bin instead of a sample (every written line of their tables is compared)."""
     from concurrent.futures import ThreadPoolExecutor
     from oracle import p7
     from oracle import reduce_oracle as ro
@@ -87,7 +88,7 @@ def verify(out_dir, table, hmm_path, bin_ids, files, models_by_bin, k_bins=3, n_
     hs = p7.HmmSet(hmm_path)
     index = {(hs.acc(i) or hs.name(i)): i for i in range(hs.n)}
     qname = {i: hs.name(i) for i in range(hs.n)}
-    pick_bins = sorted(rng.choice(len(bin_ids), size=min(k_bins, len(bin_ids)), replace=False).tolist())
+    pick_bins = sorted(set(rng.choice(len(bin_ids), size=min(k_bins, len(bin_ids)), replace=False).tolist()) | set(whole_bins))
     out = {"bins": [], "models": 0, "rows": 0, "launch_classes": 0, "identical": True, "qa_rows_identical": None, "mismatches": []}
     classes_seen = set()
     jobs = []
@@ -102,6 +103,8 @@ def verify(out_dir, table, hmm_path, bin_ids, files, models_by_bin, k_bins=3, n_
         hit_accs = sorted({name_to_acc[ln.split()[3]] for ln in table_lines(os.path.join(out_dir, "bins", binId, table)) if ln.split()[3] in name_to_acc} - set(sample))
         rng.shuffle(hit_accs)
         sample = sample + hit_accs[:with_rows]
+        if b in whole_bins:
+            sample = list(accs)
         sample = sorted(sample, key=lambda a: index[a])          # rows come in HMM-file order (hmmsearch: one query after the other)
         classes_seen |= {launch_class(lengths[a]) for a in sample}
         recs = read_fasta(files[b])
