@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcheckm_hip.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class CkmError(RuntimeError):
@@ -112,6 +112,21 @@ class NucStatsColumns(C.Structure):
                 ("ms_upload", C.c_double), ("ms_count", C.c_double), ("ms_fill", C.c_double), ("ms_total", C.c_double)]
 
 
+class TetraProfileView(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("ids", C.POINTER(C.c_char_p)), ("sig", C.POINTER(C.c_double))]
+
+
+class OutlierBounds(C.Structure):
+    _fields_ = [("ntables", C.c_uint32), ("tab_off", C.c_void_p), ("key", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p),
+                ("bin_gc_tab", C.c_void_p), ("bin_cd_tab", C.c_void_p), ("td_tab", C.c_uint32)]
+
+
+class OutlierColumns(C.Structure):
+    _fields_ = [("nseq", C.c_uint32), ("nbins", C.c_uint32)] + [(f, C.POINTER(C.c_double)) for f in ("gc", "delta_gc", "cd", "delta_cd", "td", "weight")] + \
+               [("flags", C.POINTER(C.c_uint8)), ("mean_gc", C.POINTER(C.c_double)), ("mean_cd", C.POINTER(C.c_double)), ("bin_sig", C.POINTER(C.c_double))] + \
+               [(f, C.c_double) for f in ("ms_upload", "ms_seq", "ms_binsig", "ms_td", "ms_flags", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -140,6 +155,8 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_orf_scan", "ckm_orf_columns_get", "ckm_orf_free", "ckm_debug_orf_flags", "ckm_genes_call", "ckm_genes_columns_get", "ckm_genes_free", "ckm_genes_coding_union", "ckm_genes_write_bin",
            "ckm_nuc_batch_read", "ckm_nuc_batch_view_get", "ckm_nuc_batch_free",
            "ckm_nucseq_read", "ckm_nucseq_view_get", "ckm_nucseq_free", "ckm_nucstats_run", "ckm_nucstats_columns_get", "ckm_nucstats_free", "ckm_bin_genes_read",
+           "ckm_seq_genes_read", "ckm_tetra_profile_read", "ckm_tetra_profile_view_get", "ckm_tetra_profile_gather", "ckm_tetra_profile_free",
+           "ckm_outliers_run", "ckm_outliers_columns_get", "ckm_outliers_free",
            "ckm_debug_stages", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -217,6 +234,16 @@ def load():
     L.ckm_nucstats_free.argtypes = [C.c_void_p]
     L.ckm_nucstats_free.restype = None
     L.ckm_bin_genes_read.argtypes = [C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ckm_seq_genes_read.argtypes = [C.POINTER(C.c_char_p), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ckm_tetra_profile_read.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.ckm_tetra_profile_view_get.argtypes = [C.c_void_p, C.POINTER(TetraProfileView)]
+    L.ckm_tetra_profile_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    L.ckm_tetra_profile_free.argtypes = [C.c_void_p]
+    L.ckm_tetra_profile_free.restype = None
+    L.ckm_outliers_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(OutlierBounds), C.POINTER(C.c_int64), C.POINTER(C.c_void_p)]
+    L.ckm_outliers_columns_get.argtypes = [C.c_void_p, C.POINTER(OutlierColumns)]
+    L.ckm_outliers_free.argtypes = [C.c_void_p]
+    L.ckm_outliers_free.restype = None
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -747,3 +774,91 @@ def bin_genes(seqs, gff_paths, faa_paths):
     table = np.zeros(max(1, n), dtype=np.int32)
     _chk(load().ckm_bin_genes_read(g, a, seqs.h, coding.ctypes.data, table.ctypes.data, ngenes.ctypes.data))
     return [(int(coding[k]), None if table[k] == -2 ** 31 else int(table[k]), int(ngenes[k])) for k in range(n)]
+
+
+def seq_genes(seqs, gff_paths):
+    """(coding bases per sequence of the batch [nseq] int64, missing [nfiles] bool) from bins/<binId>/genes.gff of every file
+    (ckm_seq_genes_read): ProdigalGeneFeatureParser.codingBases(seqId), -1 for the sequences of a file without a GFF."""
+    n = seqs.nfiles
+    g = (C.c_char_p * max(1, n))(*[os.fsencode(p) for p in gff_paths])
+    coding = np.zeros(max(1, seqs.nseq), dtype=np.int64)
+    missing = np.zeros(max(1, n), dtype=np.uint8)
+    _chk(load().ckm_seq_genes_read(g, seqs.h, coding.ctypes.data, missing.ctypes.data))
+    return coding[:seqs.nseq], missing[:n].astype(bool)
+
+
+class TetraProfile(object):
+    """The file GenomicSignatures.calculate writes, parsed once by the library's host threads (ckm_tetra_profile_read); every value is
+    float(token) bit for bit.  Lives in the library until close()."""
+
+    def __init__(self, path):
+        self.h = C.c_void_p()
+        _chk(load().ckm_tetra_profile_read(os.fsencode(path), C.byref(self.h)))
+        v = TetraProfileView()
+        _chk(load().ckm_tetra_profile_view_get(self.h, C.byref(v)))
+        self.n = int(v.n)
+        self._view = v
+
+    def ids(self):
+        return [self._view.ids[i].decode("utf-8") for i in range(self.n)]
+
+    def sig(self):
+        """[n, 136] float64 (a copy)."""
+        return np.ctypeslib.as_array(self._view.sig, shape=(self.n, 136)).copy() if self.n else np.zeros((0, 136))
+
+    def gather(self, seqs):
+        """([nseq, 136] rows of the batch's sequences by id, index of the first sequence the profile does not hold or -1)."""
+        out = np.zeros((max(1, seqs.nseq), 136), dtype=np.float64)
+        miss = C.c_int64(-1)
+        _chk(load().ckm_tetra_profile_gather(self.h, seqs.h, out.ctypes.data, C.byref(miss)))
+        return out[:seqs.nseq], int(miss.value)
+
+    def close(self):
+        if self.h:
+            load().ckm_tetra_profile_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def outliers(ctx, seqs, count, sig, coding, tab_off, key, lo, hi, bin_gc_tab, bin_cd_tab, td_tab):
+    """The device pass of `checkm outliers` over a NucSeqs batch (ckm_outliers_run): count = nucstats()['count'], sig = the gathered
+    profile rows, coding = seq_genes()[0]; the bound tables as include/checkm_hip.h lays them out.  Returns a dict of per-sequence
+    float64 columns gc, delta_gc, cd, delta_cd, td, weight, the flag bytes (bit 0 GC, 1 CD, 2 TD), per-bin mean_gc, mean_cd,
+    bin_sig [nbins, 136] and the timings.  Raises ZeroDivisionError where the reference does (a sequence without A, C, G, T, U)."""
+    count = np.ascontiguousarray(count, dtype=np.uint64)
+    sig = np.ascontiguousarray(sig, dtype=np.float64)
+    coding = np.ascontiguousarray(coding, dtype=np.int64)
+    assert count.shape == (seqs.nseq, 8) and sig.shape == (seqs.nseq, 136) and coding.shape == (seqs.nseq,)
+    tab_off = np.ascontiguousarray(tab_off, dtype=np.uint32)
+    key, lo, hi = (np.ascontiguousarray(x, dtype=np.float64) for x in (key, lo, hi))
+    assert len(key) == len(lo) == len(hi) == int(tab_off[-1])
+    gct, cdt = (np.ascontiguousarray(x, dtype=np.uint32) for x in (bin_gc_tab, bin_cd_tab))
+    assert len(gct) == len(cdt) == seqs.nfiles
+    keep = [np.zeros(1, dtype=x.dtype) if x.size == 0 else x for x in (count, sig, coding, gct, cdt)]
+    b = OutlierBounds(len(tab_off) - 1, tab_off.ctypes.data, key.ctypes.data, lo.ctypes.data, hi.ctypes.data, keep[3].ctypes.data, keep[4].ctypes.data, int(td_tab))
+    h = C.c_void_p()
+    zero = C.c_int64(-1)
+    rc = load().ckm_outliers_run(ctx.h, seqs.h, keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, C.byref(b), C.byref(zero), C.byref(h))
+    if rc != 0 and zero.value >= 0:
+        raise ZeroDivisionError("float division by zero")
+    _chk(rc)
+    try:
+        c = OutlierColumns()
+        _chk(load().ckm_outliers_columns_get(h, C.byref(c)))
+        n, nb = int(c.nseq), int(c.nbins)
+        arr = np.ctypeslib.as_array
+        out = {f: (arr(getattr(c, f), shape=(n,)).copy() if n else np.zeros(0)) for f in ("gc", "delta_gc", "cd", "delta_cd", "td", "weight")}
+        out["flags"] = arr(c.flags, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint8)
+        out["mean_gc"] = arr(c.mean_gc, shape=(nb,)).copy() if nb else np.zeros(0)
+        out["mean_cd"] = arr(c.mean_cd, shape=(nb,)).copy() if nb else np.zeros(0)
+        out["bin_sig"] = arr(c.bin_sig, shape=(nb, 136)).copy() if nb else np.zeros((0, 136))
+        for f in ("ms_upload", "ms_seq", "ms_binsig", "ms_td", "ms_flags", "ms_total"):
+            out[f] = getattr(c, f)
+    finally:
+        load().ckm_outliers_free(h)
+    return out

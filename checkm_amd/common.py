@@ -1,4 +1,5 @@
-"""Small filesystem helpers with the reference's semantics (checkm/common.py:33-44,136-151)."""
+"""Small helpers with the reference's semantics (checkm/common.py)."""
+import ast
 import errno
 import os
 import sys
@@ -38,6 +39,22 @@ def checkFileExists(inputFile):
     if not os.path.exists(inputFile):
         logging.getLogger('timestamp').error('Input file does not exists: ' + inputFile)
         sys.exit(1)
+
+
+def readDistribution(prefix):
+    """The dict literal of <DISTRIBUTION_DIR>/<prefix>.txt (gc_dist, cd_dist, td_dist)."""
+    from checkm_amd.defaultValues import DefaultValues
+    distFile = os.path.join(DefaultValues.DISTRIBUTION_DIR, prefix + '.txt')
+    checkFileExists(distFile)
+    with open(distFile, 'r') as f:
+        return ast.literal_eval(f.read())
+
+
+def findNearest(array, value):
+    """The element of array nearest to value; of two equally near ones the first (numpy's argmin)."""
+    import numpy as np
+    idx = (np.abs(np.array(array) - value)).argmin()
+    return array[idx]
 
 
 def read_fasta(path):

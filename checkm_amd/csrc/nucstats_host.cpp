@@ -19,7 +19,7 @@
 
 namespace ckm {
 
-static bool read_bytes(const char *path, std::string &buf, std::string &err) {
+bool read_bytes(const char *path, std::string &buf, std::string &err) {
   const size_t n = strlen(path);
   if (n > 3 && !strcmp(path + n - 3, ".gz")) {                 // readFasta opens '.gz' names with gzip.open
     gzFile g = gzopen(path, "rb");
@@ -118,17 +118,6 @@ static void parse_nuc_fasta(const char *path, NucFile &o) {
   }
 }
 
-template <class F>
-static void for_each_parallel(uint32_t n, F &&f) {
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const unsigned nt = std::min<unsigned>(std::min<unsigned>(hw, 16u), std::max(1u, n));
-  std::atomic<uint32_t> next(0);
-  auto work = [&] { for (uint32_t b; (b = next.fetch_add(1)) < n;) f(b); };
-  std::vector<std::thread> th;
-  for (unsigned k = 1; k < nt; ++k) th.emplace_back(work);
-  work();
-  for (auto &t : th) t.join();
-}
 
 // ---- the genes of one bin ----------------------------------------------------------------------------------------------------------------
 // ProdigalGeneFeatureParser (checkm_amd/prodigal.py, the restatement of checkm/prodigal.py:208-274): per sequence id the genes keyed by
@@ -136,14 +125,15 @@ static void for_each_parallel(uint32_t n, F &&f) {
 // coding base, and the union of the intervals up to it.
 struct GffSeq { std::unordered_map<long, std::pair<long long, long long>> genes; long long last = 0; };
 
-static int read_bin_genes(const char *gff, const char *faa, const std::vector<std::string> &ids, int64_t &coding, int32_t &table, int64_t &ngenes, std::string &err) {
+// The rows of one GFF file.  A file that does not exist: *missing = true and nothing else.
+static int parse_gff(const char *gff, std::unordered_map<std::string, GffSeq> &seqs, bool &have_table, long &tt, bool &missing, std::string &err) {
   struct stat sb;
-  if (stat(gff, &sb) != 0) { coding = -1; table = -1; ngenes = -1; return CKM_OK; }
+  missing = stat(gff, &sb) != 0;
+  if (missing) return CKM_OK;
   std::string buf;
   if (!read_bytes(gff, buf, err)) return CKM_EIO;
-  std::unordered_map<std::string, GffSeq> seqs;
   long counter = 0;
-  bool have_table = false; long tt = 0;
+  have_table = false; tt = 0;
   size_t i = 0; const size_t n = buf.size();
   while (i < n) {
     size_t e = i; while (e < n && buf[e] != '\n' && buf[e] != '\r') ++e;
@@ -174,24 +164,39 @@ static int read_bin_genes(const char *gff, const char *faa, const std::vector<st
     it->second.genes[counter++] = {s, z};
     it->second.last = std::max(it->second.last, z);
   }
-  // bases of the bin's sequences inside the union of their genes, clipped to [0, last coding base)
+  return CKM_OK;
+}
+
+// ProdigalGeneFeatureParser.codingBases(seqId): bases of one sequence inside the union of its genes, clipped to [0, last coding base)
+static long long coding_bases(const GffSeq &g) {
+  std::vector<std::pair<long long, long long>> iv;
+  for (auto &x : g.genes) if (x.second.second > x.second.first - 1) iv.push_back({x.second.first - 1, x.second.second});
+  std::sort(iv.begin(), iv.end());
+  const long long last = g.last;
+  long long total = 0, cs = 0, ce = -1; bool open = false;
+  auto flush = [&] { if (open) { const long long lo = std::max(cs, 0LL), hi = std::min(ce, last); if (hi > lo) total += hi - lo; } };
+  for (auto &v : iv) {
+    if (open && v.first <= ce) ce = std::max(ce, v.second);
+    else { flush(); cs = v.first; ce = v.second; open = true; }
+  }
+  flush();
+  return total;
+}
+
+static int read_bin_genes(const char *gff, const char *faa, const std::vector<std::string> &ids, int64_t &coding, int32_t &table, int64_t &ngenes, std::string &err) {
+  std::unordered_map<std::string, GffSeq> seqs;
+  bool have_table = false, missing = false; long tt = 0;
+  const int prc = parse_gff(gff, seqs, have_table, tt, missing, err);
+  if (prc) return prc;
+  if (missing) { coding = -1; table = -1; ngenes = -1; return CKM_OK; }
+  size_t i = 0;
+  // bases of the bin's sequences inside the union of their genes
   std::unordered_set<std::string> seen;
   long long total = 0;
   for (const std::string &id : ids) {
     if (!seen.insert(id).second) continue;
     auto it = seqs.find(id);
-    if (it == seqs.end()) continue;
-    std::vector<std::pair<long long, long long>> iv;
-    for (auto &g : it->second.genes) if (g.second.second > g.second.first - 1) iv.push_back({g.second.first - 1, g.second.second});
-    std::sort(iv.begin(), iv.end());
-    const long long last = it->second.last;
-    long long cs = 0, ce = -1; bool open = false;
-    auto flush = [&] { if (open) { const long long lo = std::max(cs, 0LL), hi = std::min(ce, last); if (hi > lo) total += hi - lo; } };
-    for (auto &v : iv) {
-      if (open && v.first <= ce) ce = std::max(ce, v.second);
-      else { flush(); cs = v.first; ce = v.second; open = true; }
-    }
-    flush();
+    if (it != seqs.end()) total += coding_bases(it->second);
   }
   // len(readFasta(genes.faa)): distinct ids
   std::string fbuf;
@@ -261,6 +266,32 @@ extern "C" int ckm_nucseq_view_get(const ckm_nucseq *b, ckm_nucseq_view *o) {
 }
 
 extern "C" void ckm_nucseq_free(ckm_nucseq *b) { delete b; }
+
+// Per sequence what ckm_bin_genes_read sums per file: ProdigalGeneFeatureParser.codingBases(seqId), 0 for an id without genes.
+extern "C" int ckm_seq_genes_read(const char *const *gff_paths, const ckm_nucseq *b, int64_t *coding_per_seq, uint8_t *missing) {
+  if (!gff_paths || !b || !coding_per_seq || !missing) { set_last_error("NULL argument"); return CKM_EINVAL; }
+  const uint32_t nb = (uint32_t)b->file_first.size() - 1;
+  std::vector<int> rc(nb, CKM_OK);
+  std::vector<std::string> err(nb);
+  for_each_parallel(nb, [&](uint32_t k) {
+    try {
+      if (!gff_paths[k]) { rc[k] = CKM_EINVAL; err[k] = "NULL path"; return; }
+      std::unordered_map<std::string, GffSeq> seqs;
+      bool have_table = false, miss = false; long tt = 0;
+      rc[k] = parse_gff(gff_paths[k], seqs, have_table, tt, miss, err[k]);
+      missing[k] = miss ? 1 : 0;
+      if (rc[k]) return;
+      for (uint32_t s = b->file_first[k]; s < b->file_first[k + 1]; ++s) {
+        if (miss) { coding_per_seq[s] = -1; continue; }
+        auto it = seqs.find(b->ids[s]);
+        coding_per_seq[s] = it == seqs.end() ? 0 : (int64_t)coding_bases(it->second);
+      }
+    } catch (const std::exception &e) { rc[k] = CKM_ENOMEM; err[k] = e.what(); }
+  });
+  for (uint32_t k = 0; k < nb; ++k)
+    if (rc[k]) { set_last_error(err[k]); return rc[k]; }
+  return CKM_OK;
+}
 
 extern "C" int ckm_bin_genes_read(const char *const *gff_paths, const char *const *faa_paths, const ckm_nucseq *b,
                                   int64_t *coding, int32_t *trans_table, int64_t *ngenes) {

@@ -1,10 +1,29 @@
-// nucstats_host.h -- the batch object of ckm_nucseq_read (not part of the ABI).
+// nucstats_host.h -- the batch object of ckm_nucseq_read and the host helpers its readers share (not part of the ABI).
 #pragma once
+#include <algorithm>
+#include <atomic>
 #include <cstdint>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace ckm {
+// the whole file ('.gz' names through zlib); false and a message in err when it cannot be read
+bool read_bytes(const char *path, std::string &buf, std::string &err);
+
+// f(0) .. f(n - 1) on up to 16 host threads
+template <class F>
+inline void for_each_parallel(uint32_t n, F &&f) {
+  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+  const unsigned nt = std::min<unsigned>(std::min<unsigned>(hw, 16u), std::max(1u, n));
+  std::atomic<uint32_t> next(0);
+  auto work = [&] { for (uint32_t b; (b = next.fetch_add(1)) < n;) f(b); };
+  std::vector<std::thread> th;
+  for (unsigned k = 1; k < nt; ++k) th.emplace_back(work);
+  work();
+  for (auto &t : th) t.join();
+}
+
 struct NucFile {                       // one FASTA file as readFasta leaves it: ids in first-seen order, the last record's sequence
   std::vector<std::string> ids, seqs;
   int err_code = 0;

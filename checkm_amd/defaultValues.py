@@ -21,6 +21,7 @@ class DefaultValues(object):
     PFAM_CLAN_FILE = os.path.join(CHECKM_DATA_DIR, 'pfam', 'Pfam-A.hmm.dat')
     SELECTED_MARKER_SETS = os.path.join(CHECKM_DATA_DIR, 'selected_marker_sets.tsv')
     TAXON_MARKER_SETS = os.path.join(CHECKM_DATA_DIR, 'taxon_marker_sets.tsv')
+    DISTRIBUTION_DIR = os.path.join(CHECKM_DATA_DIR, 'distributions')
 
     PHYLO_HMM_MODEL_INFO = 'phylo_hmm_info.pkl.gz'
     CHECKM_HMM_MODEL_INFO = 'checkm_hmm_info.pkl.gz'
@@ -45,3 +46,4 @@ class DefaultValues(object):
         cls.PFAM_CLAN_FILE = os.path.join(root, 'pfam', 'Pfam-A.hmm.dat')
         cls.SELECTED_MARKER_SETS = os.path.join(root, 'selected_marker_sets.tsv')
         cls.TAXON_MARKER_SETS = os.path.join(root, 'taxon_marker_sets.tsv')
+        cls.DISTRIBUTION_DIR = os.path.join(root, 'distributions')

@@ -46,3 +46,11 @@ def install():
     else:
         from checkm_amd import genomicSignatures as gs
         checkm.genomicSignatures.GenomicSignatures = gs.GenomicSignatures
+    # `checkm outliers`, `modify`, `unique`: per-sequence GC, coding density and tetranucleotide distance on the device
+    try:
+        import checkm.binTools
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import binTools as bt
+        checkm.binTools.BinTools = bt.BinTools

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 8
+#define CKM_ABI_VERSION 9
 
 enum {
   CKM_OK      =  0,
@@ -404,6 +404,62 @@ void ckm_nucstats_free(ckm_nucstats *r);
  * their genes (ProdigalGeneFeatureParser.codingBases summed over the ids), trans_table[f] = the first '# Model Data' line's transl_table
  * (INT32_MIN: none), ngenes[f] = distinct records of genes.faa; all three -1 when the GFF does not exist.  No device needed. */
 int  ckm_bin_genes_read(const char *const *gff_paths, const char *const *faa_paths, const ckm_nucseq *b, int64_t *coding, int32_t *trans_table, int64_t *ngenes);
+
+/* ---- `checkm outliers`: per-sequence GC, coding density and tetranucleotide distance against the bin (ABI 9) ----------------------------
+ * ckm_seq_genes_read replaces ProdigalGeneFeatureParser.codingBases(seqId) (checkm/prodigal.py:250-273) as
+ * BinTools.codingDensityDist calls it (checkm/binTools.py:168-184): gff_paths[f] is bins/<binId>/genes.gff of file f of the batch;
+ * coding_per_seq[s] = bases of sequence s inside the union of its genes, 0 for an id without genes.  The parsing is that of
+ * ckm_bin_genes_read: the sum over a file's sequences is what that call returns.  missing[f] = 1 and coding_per_seq = -1 for the
+ * sequences of a file whose GFF does not exist (the caller reports checkm/binTools.py:242-244).  Host threads, a file per thread. */
+int  ckm_seq_genes_read(const char *const *gff_paths, const ckm_nucseq *b, int64_t *coding_per_seq /* [nseq] */, uint8_t *missing /* [nfiles] */);
+
+/* ckm_tetra_profile_read replaces GenomicSignatures.read (checkm/genomicSignatures.py:192-200), which BinTools.identifyOutliers calls
+ * once per bin (checkm/binTools.py:236-237): the file GenomicSignatures.calculate writes, read once, its lines split over host threads.
+ * Every value equals Python's float(token) bit for bit (strtod is correctly rounded; 'nan' rows included); the first line is the header;
+ * a later row of an id replaces the earlier one, as in the dict.  A row without exactly 136 frequencies, or with a token that is not a
+ * float, is CKM_EFORMAT.  The view lives until ckm_tetra_profile_free.
+ * ckm_tetra_profile_gather: sig[s*136 ..] = the row of sequence s of the batch, looked up by id (tetraSigs[seqId],
+ * checkm/binTools.py:194,207); *first_missing = the first sequence whose id the profile does not hold (its row is zeros), or -1. */
+typedef struct ckm_tetra_profile ckm_tetra_profile;
+typedef struct {
+  uint32_t           n;
+  const char *const *ids;                   /* [n] */
+  const double      *sig;                   /* [n * 136] */
+} ckm_tetra_profile_view;
+int  ckm_tetra_profile_read(const char *path, ckm_tetra_profile **out);
+int  ckm_tetra_profile_view_get(const ckm_tetra_profile *p, ckm_tetra_profile_view *out);
+int  ckm_tetra_profile_gather(const ckm_tetra_profile *p, const ckm_nucseq *b, double *sig /* [nseq * 136] */, int64_t *first_missing);
+void ckm_tetra_profile_free(ckm_tetra_profile *p);
+
+/* The device pass: replaces gcDist, codingDensityDist, binTetraSig, tetraDiffDist's distances and the comparisons of identifyOutliers
+ * (checkm/binTools.py:148-209,263-286; GenomicSignatures.distance, checkm/genomicSignatures.py:189-190) for every bin (= file) of the
+ * batch.  count = the counters of ckm_nucstats_run ([nseq * 8]), sig = the gathered profile rows, coding_per_seq = ckm_seq_genes_read.
+ * Bounds: table t owns rows tab_off[t] .. tab_off[t+1]-1 of key / lo / hi, one row per sequence-length key in the distribution's dict
+ * order; bin k uses table bin_gc_tab[k] (lo, hi: the two percentile bounds of delta GC), bin_cd_tab[k] (lo: the lower bound of delta CD)
+ * and every bin table td_tab (hi: the bound of TD).  The caller picks the tables and percentile keys as checkm/binTools.py:249-261 does.
+ * Results are float64 and equal the reference's bit for bit (evaluation orders: checkm_amd/csrc/outlier_dev.h); flags: bit 0 GC, 1 CD,
+ * 2 TD.  A sequence without A, C, G, T, U (or a bin without sequences) is the reference's ZeroDivisionError: *zero_seq = its index and
+ * the call fails with CKM_EINVAL; otherwise *zero_seq = -1. */
+typedef struct {
+  uint32_t        ntables;
+  const uint32_t *tab_off;                  /* [ntables + 1] */
+  const double   *key, *lo, *hi;            /* [tab_off[ntables]] */
+  const uint32_t *bin_gc_tab, *bin_cd_tab;  /* [nfiles] */
+  uint32_t        td_tab;
+} ckm_outlier_bounds;
+typedef struct ckm_outliers ckm_outliers;
+typedef struct {
+  uint32_t       nseq, nbins;
+  const double  *gc, *delta_gc, *cd, *delta_cd, *td, *weight;   /* [nseq]; weight = len / bin length, the factor of binTetraSig */
+  const uint8_t *flags;                                         /* [nseq] */
+  const double  *mean_gc, *mean_cd;                             /* [nbins] */
+  const double  *bin_sig;                                       /* [nbins * 136] */
+  double         ms_upload, ms_seq, ms_binsig, ms_td, ms_flags, ms_total;   /* HIP events: upload and each kernel; wall of the call */
+} ckm_outliers_columns;
+int  ckm_outliers_run(ckm_ctx *ctx, const ckm_nucseq *b, const uint64_t *count, const double *sig, const int64_t *coding_per_seq,
+                      const ckm_outlier_bounds *bounds, int64_t *zero_seq, ckm_outliers **out);
+int  ckm_outliers_columns_get(const ckm_outliers *r, ckm_outliers_columns *out);
+void ckm_outliers_free(ckm_outliers *r);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
