@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcheckm_hip.so")
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class CkmError(RuntimeError):
@@ -127,6 +127,12 @@ class OutlierColumns(C.Structure):
                [(f, C.c_double) for f in ("ms_upload", "ms_seq", "ms_binsig", "ms_td", "ms_flags", "ms_total")]
 
 
+class MergeColumns(C.Structure):
+    _fields_ = [("npairs", C.c_uint64), ("compared", C.c_uint64), ("nbatches", C.c_uint64), ("kept", C.c_int32),
+                ("i", C.POINTER(C.c_uint32)), ("j", C.POINTER(C.c_uint32)), ("col", C.POINTER(C.c_double) * 9)] + \
+               [(f, C.c_double) for f in ("ms_upload", "ms_bins", "ms_count", "ms_scan", "ms_fill", "ms_download", "ms_write", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -157,6 +163,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_nucseq_read", "ckm_nucseq_view_get", "ckm_nucseq_free", "ckm_nucstats_run", "ckm_nucstats_columns_get", "ckm_nucstats_free", "ckm_bin_genes_read",
            "ckm_seq_genes_read", "ckm_tetra_profile_read", "ckm_tetra_profile_view_get", "ckm_tetra_profile_gather", "ckm_tetra_profile_free",
            "ckm_outliers_run", "ckm_outliers_columns_get", "ckm_outliers_free",
+           "ckm_merge_check", "ckm_merge_run", "ckm_merge_columns_get", "ckm_merge_free",
            "ckm_debug_stages", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -244,6 +251,12 @@ def load():
     L.ckm_outliers_columns_get.argtypes = [C.c_void_p, C.POINTER(OutlierColumns)]
     L.ckm_outliers_free.argtypes = [C.c_void_p]
     L.ckm_outliers_free.restype = None
+    L.ckm_merge_check.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ckm_merge_run.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_char_p, C.c_uint64, C.c_int,
+                                C.POINTER(C.c_void_p)]
+    L.ckm_merge_columns_get.argtypes = [C.c_void_p, C.POINTER(MergeColumns)]
+    L.ckm_merge_free.argtypes = [C.c_void_p]
+    L.ckm_merge_free.restype = None
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -861,4 +874,61 @@ def outliers(ctx, seqs, count, sig, coding, tab_off, key, lo, hi, bin_gc_tab, bi
             out[f] = getattr(c, f)
     finally:
         load().ckm_outliers_free(h)
+    return out
+
+
+MERGE_COLUMNS = ("comp_i", "cont_i", "comp_j", "cont_j", "delta_comp", "delta_cont", "delta", "comp_merged", "cont_merged")
+
+
+def _merge_args(member_bits, hit_sum, n_markers, ngenes, thresholds):
+    bits = np.ascontiguousarray(member_bits, dtype=np.uint64)
+    nwords = (int(ngenes) + 63) // 64
+    if bits.ndim != 2 or bits.shape[1] != max(1, nwords):
+        raise ValueError("member_bits must be [nbins, (ngenes + 63) // 64]")
+    s = np.ascontiguousarray(hit_sum, dtype=np.int64)
+    n = np.ascontiguousarray(n_markers, dtype=np.int32)
+    if s.shape != (bits.shape[0],) or n.shape != (bits.shape[0],):
+        raise ValueError("hit_sum and n_markers must hold one value per bin")
+    thr = np.ascontiguousarray([float(x) for x in thresholds], dtype=np.float64)
+    if thr.shape != (4,):
+        raise ValueError("four thresholds")
+    return bits, s, n, thr
+
+
+def merge_check(member_bits, hit_sum, n_markers, ngenes, thresholds):
+    """ckm_merge_check: the argument tests of merge_pairs(), without a device.  Raises CkmError as merge_pairs would."""
+    bits, s, n, thr = _merge_args(member_bits, hit_sum, n_markers, ngenes, thresholds)
+    _chk(load().ckm_merge_check(bits.shape[0], int(ngenes), bits.ctypes.data, s.ctypes.data, n.ctypes.data, thr.ctypes.data))
+
+
+def merge_pairs(ctx, member_bits, hit_sum, n_markers, ngenes, thresholds, bin_ids=None, append_path=None, budget_bytes=0, keep_columns=True):
+    """The all-pairs comparison of `checkm merge` (ckm_merge_run): member_bits [nbins, nwords] uint64, one row per bin in output order;
+    thresholds = (minDeltaComp, maxDeltaCont, minMergedComp, maxMergedCont).  append_path: the lines of the reported pairs are appended
+    to that file (bin_ids: the encoded ids).  Returns a dict: npairs, compared, nbatches, the timings and, with keep_columns, i, j and
+    the nine float64 columns of MERGE_COLUMNS."""
+    bits, s, n, thr = _merge_args(member_bits, hit_sum, n_markers, ngenes, thresholds)
+    nb = bits.shape[0]
+    ids = None
+    if bin_ids is not None:
+        if len(bin_ids) != nb:
+            raise ValueError("one id per bin")
+        ids = (C.c_char_p * max(1, nb))(*[b if isinstance(b, bytes) else b.encode() for b in bin_ids])
+    h = C.c_void_p()
+    _chk(load().ckm_merge_run(ctx.h, nb, int(ngenes), bits.ctypes.data, s.ctypes.data, n.ctypes.data, thr.ctypes.data, ids,
+                              os.fsencode(append_path) if append_path is not None else None, int(budget_bytes), 1 if keep_columns else 0, C.byref(h)))
+    try:
+        c = MergeColumns()
+        _chk(load().ckm_merge_columns_get(h, C.byref(c)))
+        out = dict(npairs=int(c.npairs), compared=int(c.compared), nbatches=int(c.nbatches))
+        for f in ("ms_upload", "ms_bins", "ms_count", "ms_scan", "ms_fill", "ms_download", "ms_write", "ms_total"):
+            out[f] = getattr(c, f)
+        if c.kept:
+            k = out["npairs"]
+            arr = np.ctypeslib.as_array
+            out["i"] = arr(c.i, shape=(k,)).copy() if k else np.zeros(0, dtype=np.uint32)
+            out["j"] = arr(c.j, shape=(k,)).copy() if k else np.zeros(0, dtype=np.uint32)
+            for q, f in enumerate(MERGE_COLUMNS):
+                out[f] = arr(c.col[q], shape=(k,)).copy() if k else np.zeros(0)
+    finally:
+        load().ckm_merge_free(h)
     return out

@@ -54,3 +54,11 @@ def install():
     else:
         from checkm_amd import binTools as bt
         checkm.binTools.BinTools = bt.BinTools
+    # `checkm merge`: the all-pairs comparison of marker genes on the device
+    try:
+        import checkm.merger
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import merger as mg
+        checkm.merger.Merger = mg.Merger

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 9
+#define CKM_ABI_VERSION 10
 
 enum {
   CKM_OK      =  0,
@@ -460,6 +460,34 @@ int  ckm_outliers_run(ckm_ctx *ctx, const ckm_nucseq *b, const uint64_t *count, 
                       const ckm_outlier_bounds *bounds, int64_t *zero_seq, ckm_outliers **out);
 int  ckm_outliers_columns_get(const ckm_outliers *r, ckm_outliers_columns *out);
 void ckm_outliers_free(ckm_outliers *r);
+
+/* ---- `checkm merge`: the all-pairs comparison of marker genes (ABI 10) -------------------------------------------------------------------
+ * Replaces the double loop of Merger.run (checkm/merger.py:64-106), which builds a merged hit dict and calls geneCounts for every pair
+ * of bins.  A bin is: member_bits[b * nwords ..], nwords = (ngenes + 63) / 64, bit g set when marker gene g of the common gene set is a
+ * key of the bin's hit dict (a key with an empty list counts); hit_sum[b] = hits to those genes; n_markers[b] = numMarkers() of the
+ * bin's most specific marker set.  thr = {minDeltaComp, maxDeltaCont, minMergedComp, maxMergedCont}.  For every pair i < j, in (i, j)
+ * order, the device applies merger.py:92 and :100 in float64 (evaluation order: checkm_amd/csrc/merge_dev.h; the merged pair is judged
+ * by bin j's n_markers) and reports the pairs that pass, bit-equal to the reference.
+ * append_path != NULL: the lines of the reported pairs ('%s\t%s' + 9 x '\t%.2f') are appended to that file, ids from bin_ids[nbins].
+ * keep_columns != 0: the columns stay with the result (ckm_merge_columns_get); otherwise only the counts and timings do.
+ * The output goes through the device in batches of whole rows of at most budget_bytes (0: CKM_MERGE_BATCH_MB, default 256, << 20);
+ * the batches never change the result.  Refused with CKM_EINVAL, nothing computed: a NULL argument, ngenes == 0, n_markers[b] <= 0,
+ * hit_sum[b] < 0, a member bit at or beyond ngenes.  ckm_merge_check applies the same tests and needs no device. */
+typedef struct ckm_merge ckm_merge;
+typedef struct {
+  uint64_t        npairs;                   /* reported pairs */
+  uint64_t        compared;                 /* nbins * (nbins - 1) / 2 */
+  uint64_t        nbatches;                 /* output batches the fill pass ran in */
+  int32_t         kept;                     /* 1: the columns below are there */
+  const uint32_t *i, *j;                    /* [npairs] */
+  const double   *col[9];                   /* [npairs] each: compI, contI, compJ, contJ, deltaComp, deltaCont, delta, compM, contM */
+  double          ms_upload, ms_bins, ms_count, ms_scan, ms_fill, ms_download, ms_write, ms_total;   /* HIP events per phase (scan: with the host's row prefix); write and total: wall */
+} ckm_merge_columns;
+int  ckm_merge_check(uint32_t nbins, uint32_t ngenes, const uint64_t *member_bits, const int64_t *hit_sum, const int32_t *n_markers, const double *thr);
+int  ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, const uint64_t *member_bits, const int64_t *hit_sum, const int32_t *n_markers,
+                   const double *thr /* [4] */, const char *const *bin_ids, const char *append_path, uint64_t budget_bytes, int keep_columns, ckm_merge **out);
+int  ckm_merge_columns_get(const ckm_merge *r, ckm_merge_columns *out);
+void ckm_merge_free(ckm_merge *r);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
