@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcheckm_hip.so")
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class CkmError(RuntimeError):
@@ -164,7 +164,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_seq_genes_read", "ckm_tetra_profile_read", "ckm_tetra_profile_view_get", "ckm_tetra_profile_gather", "ckm_tetra_profile_free",
            "ckm_outliers_run", "ckm_outliers_columns_get", "ckm_outliers_free",
            "ckm_merge_check", "ckm_merge_run", "ckm_merge_columns_get", "ckm_merge_free",
-           "ckm_debug_stages", "ckm_debug_envelopes", "ckm_debug_region"]
+           "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
 
@@ -259,6 +259,8 @@ def load():
     L.ckm_merge_free.restype = None
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+    L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p]
     L.ckm_debug_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.c_void_p]
     L.ckm_debug_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -508,6 +510,19 @@ def debug_stages(ctx, profiles, seqs, model, seq):
     out = (StageScores * len(model))()
     _chk(load().ckm_debug_stages(ctx.h, profiles.h, seqs.h, model.ctypes.data, seq.ctypes.data, len(model), out))
     return out
+
+
+def debug_ssv(ctx, profiles, seqs, model, seq, per_block=0, lanes=0):
+    """The SSV kernel as the search launches it, one model against `seq` in the given order: (Smax uint16[n], route uint8[n] -- 0 dropped,
+    1 survivor, 2 exact MSV kernel --, usc float32[n] of the survivors, {cls, threads, per_block, nblocks})."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    smax = np.zeros(len(seq), dtype=np.uint16)
+    route = np.zeros(len(seq), dtype=np.uint8)
+    usc = np.zeros(len(seq), dtype=np.float32)
+    info = np.zeros(4, dtype=np.int32)
+    _chk(load().ckm_debug_ssv(ctx.h, profiles.h, seqs.h, int(model), seq.ctypes.data, len(seq), int(per_block), int(lanes), smax.ctypes.data,
+                              route.ctypes.data, usc.ctypes.data, info.ctypes.data))
+    return smax, route, usc, dict(cls=int(info[0]), threads=int(info[1]), per_block=int(info[2]), nblocks=int(info[3]))
 
 
 def debug_envelopes(ctx, profiles, seqs, model, seq, ienv, jenv):

@@ -113,6 +113,80 @@ extern "C" int ckm_debug_stages(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_
   });
 }
 
+// The SSV kernel the way the search runs it: ONE model against a list of sequences in the caller's order, blocks of per_block sequences
+// built as ckm_search.hip builds them (list_start, count, pair_start; ssv_threads_for(cls) threads), so every wavefront slot, several
+// rounds per wavefront, a partly filled last group and several blocks are exercised -- and the fused finish (ssv_finish), which
+// ckm_debug_stages never runs.  Two launches: Smax per pair (epi.maxv set), then the product's epilogue with tables sized for every pair.
+extern "C" int ckm_debug_ssv(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_seqs *s, uint32_t model, const uint32_t *seq, uint32_t n,
+                             uint32_t per_block, int32_t lanes, uint16_t *smax, uint8_t *route, float *usc, int32_t *info) {
+  return guarded([&] {
+    if (!ctx_ || !p || !s || !seq || !smax || !route || !usc) throw Error(CKM_EINVAL, "NULL argument");
+    if (model >= p->hmm.size()) throw Error(CKM_EINVAL, "model index out of range");
+    if (p->too_long[model]) throw Error(CKM_ERANGE, "model longer than the instantiated kernel classes");
+    if (n == 0 || n > (1u << 24)) throw Error(CKM_EINVAL, "between 1 and 2^24 sequences");
+    if (lanes != 0 && lanes != 8 && lanes != 16) throw Error(CKM_EINVAL, "lanes must be 0, 8 or 16");
+    std::vector<int64_t> pos_of(s->nseq, -1);
+    for (uint32_t i = 0; i < n; ++i) {
+      if (seq[i] >= s->nseq) throw Error(CKM_EINVAL, "sequence index out of range");
+      if (s->len[seq[i]] <= 0) throw Error(CKM_EINVAL, "empty sequence (the lists of a search hold none)");
+      if (pos_of[seq[i]] >= 0) throw Error(CKM_EINVAL, "sequence listed twice");
+      pos_of[seq[i]] = i;
+    }
+    const HostProfile &hp = p->prof[model];
+    int cls = ssv_class(hp);
+    if (lanes == 8) { if (!hp.ssv8Q) throw Error(CKM_ERANGE, "the model has no 8-lane SSV image"); cls = 100 + hp.ssv8Q; }
+    if (lanes == 16) { if (hp.ssvQ > 64) throw Error(CKM_ERANGE, "the model has no 16-lane SSV image"); cls = hp.ssvQ; }
+    const uint32_t pb = per_block ? per_block : ssv_per_block(cls);
+    const int threads = ssv_threads_for(cls);
+    std::vector<SsvBlockWork> work;
+    for (uint32_t a = 0; a < n; a += pb) { SsvBlockWork w; w.model = model; w.list_start = a; w.count = std::min(pb, n - a); w.pair_start = a; work.push_back(w); }
+    if (info) { info[0] = cls; info[1] = threads; info[2] = (int32_t)pb; info[3] = (int32_t)work.size(); }
+    ctx_->settle();
+    Worker *ctx = &ctx_->w[0];
+    ctx->plan_key.clear();                 // this entry overwrites the worker's SSV tables
+    HIPCHK(hipSetDevice(ctx->device));
+    const DevModel *dm = p->d_models.as<DevModel>();
+    const LenEntry *lt = s->d_lentab.as<LenEntry>();
+    const uint8_t *res = s->d_res.as<uint8_t>();
+    const uint64_t *off = s->d_off.as<uint64_t>();
+    const int32_t *dlen = s->d_len.as<int32_t>();
+    ctx->work.ensure(work.size() * sizeof(SsvBlockWork)); ctx->idx.ensure((size_t)n * 4); ctx->maxv.ensure((size_t)n * 2 + 64);
+    ctx->surv.ensure((size_t)n * sizeof(PairRec)); ctx->nores.ensure((size_t)n * sizeof(PairRec)); ctx->counters.ensure(64);
+    wcopy(ctx, ctx->work.p, work.data(), work.size() * sizeof(SsvBlockWork), hipMemcpyHostToDevice);
+    wcopy(ctx, ctx->idx.p, seq, (size_t)n * 4, hipMemcpyHostToDevice);
+    HIPCHK(hipMemsetAsync(ctx->maxv.p, 0xff, (size_t)n * 2, ctx->stream));          // 0xffff: "the kernel wrote nothing for this pair"
+    HIPCHK(hipMemsetAsync(ctx->counters.p, 0, 64, ctx->stream));
+    SsvEpi epi; memset(&epi, 0, sizeof(epi));
+    epi.lentab = lt; epi.maxv = ctx->maxv.as<uint16_t>();
+    if (launch_ssv(cls, (int)work.size(), threads, ctx->stream, ctx->work.as<SsvBlockWork>(), dm, res, off, dlen, ctx->idx.as<uint32_t>(), epi))
+      throw Error(CKM_ERANGE, "no SSV kernel instance");
+    const SsvEpi fin{lt, ctx->surv.as<PairRec>(), ctx->counters.as<uint32_t>(), n, ctx->nores.as<PairRec>(), ctx->counters.as<uint32_t>() + 1, n, nullptr};
+    if (launch_ssv(cls, (int)work.size(), threads, ctx->stream, ctx->work.as<SsvBlockWork>(), dm, res, off, dlen, ctx->idx.as<uint32_t>(), fin))
+      throw Error(CKM_ERANGE, "no SSV kernel instance");
+    HIPCHK(hipGetLastError());
+    uint32_t cnt[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(smax, ctx->maxv.p, (size_t)n * 2, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(cnt, ctx->counters.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (cnt[0] > n || cnt[1] > n) throw Error(CKM_EHIP, "the SSV finish appended " + std::to_string(cnt[0]) + " survivors and " + std::to_string(cnt[1]) + " exact-kernel pairs for " + std::to_string(n) + " pairs");
+    std::vector<PairRec> sv(cnt[0]), nr(cnt[1]);
+    if (cnt[0]) wcopy(ctx, sv.data(), ctx->surv.p, (size_t)cnt[0] * sizeof(PairRec), hipMemcpyDeviceToHost);
+    if (cnt[1]) wcopy(ctx, nr.data(), ctx->nores.p, (size_t)cnt[1] * sizeof(PairRec), hipMemcpyDeviceToHost);
+    for (uint32_t i = 0; i < n; ++i) {
+      if (smax[i] == 0xffffu) throw Error(CKM_EHIP, "the SSV kernel wrote no Smax for list entry " + std::to_string(i));
+      route[i] = 0; usc[i] = 0.f;
+    }
+    auto place = [&](const PairRec &r, uint8_t code) {
+      if (r.model != model || r.seq >= s->nseq || pos_of[r.seq] < 0) throw Error(CKM_EHIP, "the SSV finish reported a pair that was not listed: model " + std::to_string(r.model) + ", sequence " + std::to_string(r.seq));
+      const size_t i = (size_t)pos_of[r.seq];
+      if (route[i] != 0) throw Error(CKM_EHIP, "the SSV finish reported list entry " + std::to_string(i) + " twice");
+      route[i] = code; usc[i] = r.usc;
+    };
+    for (const PairRec &r : sv) place(r, 1);
+    for (const PairRec &r : nr) place(r, 2);
+  });
+}
+
 extern "C" int ckm_debug_envelopes(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_seqs *s, const uint32_t *model, const uint32_t *seq,
                                    const int32_t *ienv, const int32_t *jenv, uint32_t n, ckm_envelope_result *out) {
   return guarded([&] {

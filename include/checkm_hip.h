@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 10
+#define CKM_ABI_VERSION 11
 
 enum {
   CKM_OK      =  0,
@@ -498,6 +498,15 @@ typedef struct {
 } ckm_stage_scores;
 int ckm_debug_stages(ckm_ctx *ctx, const ckm_profiles *p, const ckm_seqs *s,
                      const uint32_t *model, const uint32_t *seq, uint32_t npairs, ckm_stage_scores *out);
+/* The SSV kernel as the search launches it (ABI 11): ONE model against seq[n] in the caller's order, cut into blocks of per_block sequences
+ * (0: what the search uses for the model's launch class) whose tables are built as the search builds them.  lanes = 0: the launch class
+ * the search picks; 8 or 16: that mapping's instance where the model has its image, else CKM_ERANGE.  Two launches: one stores Smax per
+ * pair (smax[n], 0..256), one runs the fused finish of the MSV stage with tables sized for every pair: route[n] = 0 dropped, 1 survivor
+ * (usc[n] = its score in nats, +inf on byte overflow), 2 handed to the exact MSV kernel.  info[4] (may be NULL) = launch class, threads per
+ * block, sequences per block, blocks.  CKM_EINVAL: an empty sequence or one listed twice.  CKM_EHIP with a message naming the list
+ * entry: the device reported a pair twice (or in both tables), a pair that was not listed, or no Smax for a pair. */
+int ckm_debug_ssv(ckm_ctx *ctx, const ckm_profiles *p, const ckm_seqs *s, uint32_t model, const uint32_t *seq, uint32_t n,
+                  uint32_t per_block, int32_t lanes, uint16_t *smax, uint8_t *route, float *usc, int32_t *info);
 typedef struct {
   float envsc, oasc, fwd_xC; int32_t nscale; float null2[20];
   int32_t hmm_from, hmm_to, ali_from, ali_to; int32_t ok;

@@ -69,6 +69,9 @@ def lib():
         L.p7o_get_simd.restype = C.c_int
         L.p7o_msv_probe.restype = C.c_int64
         L.p7o_msv_probe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
+        L.p7o_msv_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.p7o_ssv_smax.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.p7o_msv_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.p7o_ensemble_seed.restype = C.c_uint32
         L.p7o_ensemble_seed.argtypes = [C.c_int]
         L.p7o_region_ensemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -82,6 +85,23 @@ def set_simd(on):
     bench.py's cpu_baseline times the search that way (kind "port-simd").  Returns whether it is in force (False on a CPU without AVX2)."""
     lib().p7o_set_simd(1 if on else 0)
     return bool(lib().p7o_get_simd())
+
+
+def _concat(seqs):
+    offs = np.zeros(len(seqs) + 1, dtype=np.int64)
+    for k, s in enumerate(seqs):
+        offs[k + 1] = offs[k] + len(s)
+    cat = np.ascontiguousarray(np.concatenate(seqs) if len(seqs) else np.zeros(0, dtype=np.uint8), dtype=np.uint8)
+    return cat, offs
+
+
+def ssv_smax(cost, bias, seqs):
+    """Single-segment ungapped Viterbi in plain integers (ceiling 256) of every digitized sequence over cost[29][M]."""
+    cost = np.ascontiguousarray(cost, dtype=np.uint8)
+    cat, offs = _concat(seqs)
+    out = np.zeros(len(seqs), dtype=np.int32)
+    lib().p7o_ssv_smax(cost.ctypes.data, cost.shape[1], int(bias), cat.ctypes.data, offs.ctypes.data, len(seqs), out.ctypes.data)
+    return out
 
 
 def digitize(text):
@@ -188,6 +208,23 @@ class HmmSet(object):
         chk = C.c_int64()
         cells = lib().p7o_msv_probe(self.h, mi.ctypes.data, len(mi), cat.ctypes.data, offs.ctypes.data, len(seqs), C.byref(chk))
         return int(cells), int(chk.value)
+
+    def msv_costs(self, i, lengths):
+        """The byte costs of model i's MSV filter: ({base, bias, tbm, tec}, cost[29][M] with node k at k - 1, tjb per length)."""
+        M = self.M(i)
+        sc = np.zeros(4, dtype=np.int32)
+        cost = np.zeros((29, M), dtype=np.uint8)
+        L = np.ascontiguousarray(lengths, dtype=np.int32)
+        tjb = np.zeros(len(L), dtype=np.int32)
+        lib().p7o_msv_costs(self.model(i), sc.ctypes.data, cost.ctypes.data, L.ctypes.data, len(L), tjb.ctypes.data)
+        return dict(base=int(sc[0]), bias=int(sc[1]), tbm=int(sc[2]), tec=int(sc[3])), cost, tjb
+
+    def msv_stage(self, i, seqs):
+        """The MSV stage alone of model i against every sequence: (msv_xJ, msv_sc, pass_msv) arrays, as stages() reports them."""
+        cat, offs = _concat(seqs)
+        xJ = np.zeros(len(seqs), dtype=np.int32); sc = np.zeros(len(seqs), dtype=np.float32); ok = np.zeros(len(seqs), dtype=np.int32)
+        lib().p7o_msv_stage(self.model(i), cat.ctypes.data, offs.ctypes.data, len(seqs), xJ.ctypes.data, sc.ctypes.data, ok.ctypes.data)
+        return xJ, sc, ok
 
     def format_domtblout(self, rows, names, descs):
         arr = (Row * max(1, len(rows)))(*rows)

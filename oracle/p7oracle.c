@@ -1479,6 +1479,61 @@ int64_t p7o_msv_probe(const P7O_HMMSET *set, const int32_t *model_idx, int nmode
   return cells;
 }
 
+/* The byte costs of the MSV filter of one model, for the plain SSV reference of tests/ssv_reference.py: scalars = {base, bias, tbm, tec},
+ * cost[x * M + k - 1] = the biased emission cost of symbol x (0..28) at node k (1..M), tjb[i] = the N/J/C move cost at length L[i]. */
+int p7o_msv_costs(const P7O_HMM *hmm, int32_t *scalars, uint8_t *cost, const int32_t *L, int nL, int32_t *tjb)
+{
+  PROF *p = prof_create(hmm);
+  const int M = p->M;
+  scalars[0] = p->base_b; scalars[1] = p->bias_b; scalars[2] = p->tbm_b; scalars[3] = p->tec_b;
+  for (int x = 0; x < P7O_KP; x++) for (int k = 1; k <= M; k++) cost[(size_t)x * M + k - 1] = p->rbv[x*(M+1)+k];
+  for (int i = 0; i < nL; i++) { LENCFG lc; lencfg(p, L[i], 1, &lc); tjb[i] = lc.tjb_b; }
+  prof_free(p);
+  return 0;
+}
+
+/* Single-segment ungapped Viterbi in plain integers, from a caller-supplied cost table (cost[x * M + k - 1], as p7o_msv_costs lays it
+ * out): U(i,k) = min(256, max(0, U(i-1,k-1) + bias - cost[x_i][k])), U(.,0) = U(0,.) = 0; smax[s] = the largest U of sequence s. */
+int p7o_ssv_smax(const uint8_t *cost, int M, int bias, const uint8_t *dsq, const int64_t *offsets, int nseq, int32_t *smax)
+{
+  int32_t *U = malloc(sizeof(int32_t) * ((size_t)M + 1));
+  for (int s = 0; s < nseq; s++) {
+    const uint8_t *x = dsq + offsets[s]; const int L = (int)(offsets[s+1] - offsets[s]);
+    int best = 0;
+    for (int k = 0; k <= M; k++) U[k] = 0;
+    for (int i = 0; i < L; i++) {
+      const uint8_t *c = cost + (size_t)x[i] * M;
+      for (int k = M; k >= 1; k--) {                 /* descending: U[k-1] still holds row i-1 */
+        int v = U[k-1] + bias - (int)c[k-1];
+        v = v < 0 ? 0 : (v > 256 ? 256 : v);
+        U[k] = v; if (v > best) best = v;
+      }
+    }
+    smax[s] = best;
+  }
+  free(U);
+  return 0;
+}
+
+/* The MSV stage alone of one model against many sequences: what p7o_stages reports as msv_xJ, msv_sc and pass_msv, without the
+ * later stages (the profile is configured once). */
+int p7o_msv_stage(const P7O_HMM *hmm, const uint8_t *dsq, const int64_t *offsets, int nseq, int32_t *xJ_out, float *sc_out, int32_t *pass_out)
+{
+  PROF *p = prof_create(hmm);
+  const float *ev = hmm->evparam;
+  for (int s = 0; s < nseq; s++) {
+    int L = (int)(offsets[s+1] - offsets[s]);
+    LENCFG lc; lencfg(p, L, 1, &lc);
+    int xJ; float usc;
+    msv_filter(p, &lc, dsq + offsets[s], L, &xJ, &usc);
+    float seq_score = (float)((double)(usc - lc.nullsc) / LOG2C);
+    double P = gumbel_surv(seq_score, ev[P7O_MMU], ev[P7O_MLAMBDA]);
+    xJ_out[s] = xJ; sc_out[s] = usc; pass_out[s] = !(P > F1);
+  }
+  prof_free(p);
+  return 0;
+}
+
 /* ------------------------------------------------------------------------------------------
  * domtblout text (column contract: checkm/hmmer.py:184-200, 255-285)
  * ------------------------------------------------------------------------------------------ */

@@ -109,6 +109,14 @@ int  p7o_get_simd(void);
 /* the MSV filter alone over every pair: cells scored (return) and the sum of the final bytes (*checksum) */
 int64_t p7o_msv_probe(const P7O_HMMSET *set, const int32_t *model_idx, int nmodels, const uint8_t *dsq, const int64_t *offsets, int nseq, int64_t *checksum);
 
+/* the byte costs of one model's MSV filter (tests/ssv_reference.py): scalars[4] = base, bias, tbm, tec; cost[29 * M], symbol-major,
+ * node k at k - 1; tjb[i] = the N/J/C move cost at length L[i] */
+int p7o_msv_costs(const P7O_HMM *hmm, int32_t *scalars, uint8_t *cost, const int32_t *L, int nL, int32_t *tjb);
+/* single-segment ungapped Viterbi in plain integers over a caller-supplied cost table (layout of p7o_msv_costs), ceiling 256 */
+int p7o_ssv_smax(const uint8_t *cost, int M, int bias, const uint8_t *dsq, const int64_t *offsets, int nseq, int32_t *smax);
+/* the MSV stage alone (p7o_stages' msv_xJ, msv_sc, pass_msv) of one model against nseq sequences */
+int p7o_msv_stage(const P7O_HMM *hmm, const uint8_t *dsq, const int64_t *offsets, int nseq, int32_t *xJ, float *sc, int32_t *pass);
+
 /* canonical-order float DP pieces exposed for kernel unit parity */
 int p7o_envelope(const P7O_HMM *hmm, const uint8_t *dsq, int L_full, int ienv, int jenv,
                  float *envsc, float *oasc, float *null2 /*[20]*/, int32_t *coords /*[4] hmmfrom,hmmto,alifrom,alito*/,

@@ -11,6 +11,7 @@ from checkm_amd import _lib
 from synthdata import synth
 from oracle import p7
 from tests import common
+from tests import ssv_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +36,19 @@ def world(gpu_ctx):
     prof.close(); seqs.close(); hs.close()
 
 
+def _want_smax(hs, dsq, pairs):
+    """Smax of every (model, sequence) pair from the plain SSV reference (tests/ssv_reference.py); 0 for a model no SSV instance holds."""
+    by_model = {}
+    for m, s in pairs:
+        by_model.setdefault(int(m), set()).add(int(s))
+    want = {}
+    for m, ss in by_model.items():
+        ss = sorted(ss)
+        sm = ssv_reference.smax_of(hs, m, [dsq[s] for s in ss]) if hs.M(m) <= 2048 else np.zeros(len(ss), dtype=np.int32)
+        want.update(((m, s), int(v)) for s, v in zip(ss, sm))
+    return want
+
+
 def _cmp_stage(o, g, f):
     a, b = getattr(o, f), getattr(g, f)
     if isinstance(a, float):
@@ -50,12 +64,15 @@ def test_stage_scores_bit_exact(world):
     pairs += [(m, nseq - k) for m in range(w["hs"].n) for k in range(1, 6)]          # edge sequences vs every model
     model = np.array([p[0] for p in pairs]); seq = np.array([p[1] for p in pairs])
     got = _lib.debug_stages(w["ctx"], w["prof"], w["seqs"], model, seq)
+    smax = _want_smax(w["hs"], w["dsq"], pairs)
     bad = []
     for i, (m, s) in enumerate(pairs):
         o = w["hs"].stages(m, w["dsq"][s])
         for f in STAGE_FIELDS:
             if not _cmp_stage(o, got[i], f):
                 bad.append((m, s, f, getattr(o, f), getattr(got[i], f)))
+        if got[i].ssv_maxv != smax[(m, s)]:
+            bad.append((m, s, "ssv_maxv", smax[(m, s)], got[i].ssv_maxv))
         # the packed exact-MSV kernel (the one the search runs on the pairs SSV cannot decide) against the same oracle bytes
         if got[i].msvp_xJ != o.msv_xJ or common.float_bits(got[i].msvp_sc) != common.float_bits(o.msv_sc):
             bad.append((m, s, "msv packed", o.msv_xJ, got[i].msvp_xJ, o.msv_sc, got[i].msvp_sc))
@@ -72,12 +89,15 @@ def test_planted_pairs_bit_exact(world):
                 pairs.append((m, s))
     model = np.array([p[0] for p in pairs]); seq = np.array([p[1] for p in pairs])
     got = _lib.debug_stages(w["ctx"], w["prof"], w["seqs"], model, seq)
+    smax = _want_smax(w["hs"], w["dsq"], pairs)
     bad = []
     for i, (m, s) in enumerate(pairs):
         o = w["hs"].stages(m, w["dsq"][s])
         for f in STAGE_FIELDS:
             if not _cmp_stage(o, got[i], f):
                 bad.append((m, s, f, getattr(o, f), getattr(got[i], f)))
+        if got[i].ssv_maxv != smax[(m, s)]:
+            bad.append((m, s, "ssv_maxv", smax[(m, s)], got[i].ssv_maxv))
         if got[i].msvp_xJ != o.msv_xJ or common.float_bits(got[i].msvp_sc) != common.float_bits(o.msv_sc):
             bad.append((m, s, "msv packed", o.msv_xJ, got[i].msvp_xJ, o.msv_sc, got[i].msvp_sc))
     assert len(pairs) > 20
@@ -186,10 +206,12 @@ def test_large_models_and_error_paths(gpu_ctx, tmp_path):
     dsq = [p7.digitize(r[2]) for r in recs]
     pairs = [(m, s) for m in range(hs.n) for s in range(len(recs))]
     got = _lib.debug_stages(gpu_ctx, prof, seqs, np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs]))
+    smax = _want_smax(hs, dsq, pairs)
     for i, (m, s) in enumerate(pairs):
         o = hs.stages(m, dsq[s])
         for f in STAGE_FIELDS:
             assert _cmp_stage(o, got[i], f), (m, s, f, getattr(o, f), getattr(got[i], f))
+        assert got[i].ssv_maxv == smax[(m, s)], (m, s, "ssv_maxv", smax[(m, s)], got[i].ssv_maxv)
     hits = _lib.search(gpu_ctx, prof, seqs)
     rows = hs.search(list(range(hs.n)), dsq, [r[0] for r in recs])
     assert hits.n == len(rows) >= 2
@@ -389,12 +411,15 @@ def test_register_class_boundaries(gpu_ctx):
     dsq = [p7.digitize(r[2]) for r in recs]
     pairs = [(m, s) for m in range(hs.n) for s in range(len(recs))]
     got = _lib.debug_stages(gpu_ctx, prof, seqs, np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs]))
+    smax = _want_smax(hs, dsq, pairs)
     bad = []
     for i, (m, s) in enumerate(pairs):
         o = hs.stages(m, dsq[s])
         for f in STAGE_FIELDS:
             if not _cmp_stage(o, got[i], f):
                 bad.append((lengths[m], recs[s][0], f, getattr(o, f), getattr(got[i], f)))
+        if got[i].ssv_maxv != smax[(m, s)]:
+            bad.append((lengths[m], recs[s][0], "ssv_maxv", smax[(m, s)], got[i].ssv_maxv))
         if got[i].msvp_xJ != o.msv_xJ or common.float_bits(got[i].msvp_sc) != common.float_bits(o.msv_sc):
             bad.append((lengths[m], recs[s][0], "msv packed", o.msv_xJ, got[i].msvp_xJ))
     assert not bad, bad[:10]

@@ -76,10 +76,15 @@ def lg(x):                       # natural log of a double, to float (the oracle
     return F(math.log(float(x))) if float(x) > 0 else F(-np.inf)
 
 
-def msv_bytes(M, mat, dsq, L):
-    """Byte the MSV filter ends with (xJ), or None when a row saturates."""
-    S = F(3.0 / math.log(2.0))
-    cost = lambda sc: -1.0 * float(_m.roundf(F(S * F(sc))))              # third-bits, as a cost
+def _third_bits(sc):
+    """A score in nats as a cost in thirds of a bit."""
+    return -1.0 * float(_m.roundf(F(F(3.0 / math.log(2.0)) * F(sc))))
+
+
+def msv_model_costs(M, mat):
+    """The byte costs of a model's MSV filter: (bias, emission_cost(k, x) for the 20 standard residues, entry, leave).  Shared by
+    msv_bytes below and by tests/test_ssv_reference_host.py, which checks the oracle's cost accessor against them."""
+    cost = _third_bits
     best = max([0.0] + [float(lg(float(mat[k][x]) / BG[x])) for k in range(1, M + 1) for x in range(20)])
     bias = int(min(255.0, cost(F(-1.0 * best))))
     def emission_cost(k, x):
@@ -87,7 +92,18 @@ def msv_bytes(M, mat, dsq, L):
         return 255 if c > 255 - bias else int(c) + bias
     entry = int(min(255.0, cost(_m.logf(F(2.0) / F(F(M) * F(M + 1))))))
     leave = int(min(255.0, cost(_m.logf(F(0.5)))))
-    move = int(min(255.0, cost(_m.logf(F(3.0) / F(L + 3)))))
+    return bias, emission_cost, entry, leave
+
+
+def msv_move_cost(L):
+    """The byte cost of leaving N / J / C at target length L."""
+    return int(min(255.0, _third_bits(_m.logf(F(3.0) / F(L + 3)))))
+
+
+def msv_bytes(M, mat, dsq, L):
+    """Byte the MSV filter ends with (xJ), or None when a row saturates."""
+    bias, emission_cost, entry, leave = msv_model_costs(M, mat)
+    move = msv_move_cost(L)
     base = 190
     em = {(k, x): emission_cost(k, x) for k in range(1, M + 1) for x in set(dsq)}
     both = (move + entry) & 0xff                                           # (the two costs are added in a byte register)
