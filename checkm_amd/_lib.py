@@ -11,7 +11,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcheckm_hip.so")
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class CkmError(RuntimeError):
@@ -164,7 +164,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_seq_genes_read", "ckm_tetra_profile_read", "ckm_tetra_profile_view_get", "ckm_tetra_profile_gather", "ckm_tetra_profile_free",
            "ckm_outliers_run", "ckm_outliers_columns_get", "ckm_outliers_free",
            "ckm_merge_check", "ckm_merge_run", "ckm_merge_columns_get", "ckm_merge_free",
-           "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_envelopes", "ckm_debug_region"]
+           "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
 
@@ -261,6 +261,8 @@ def load():
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]
+    L.ckm_debug_filters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_uint32,
+                                    C.c_void_p, C.POINTER(C.c_uint32)]
     L.ckm_debug_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.c_void_p]
     L.ckm_debug_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -523,6 +525,26 @@ def debug_ssv(ctx, profiles, seqs, model, seq, per_block=0, lanes=0):
     _chk(load().ckm_debug_ssv(ctx.h, profiles.h, seqs.h, int(model), seq.ctypes.data, len(seq), int(per_block), int(lanes), smax.ctypes.data,
                               route.ctypes.data, usc.ctypes.data, info.ctypes.data))
     return smax, route, usc, dict(cls=int(info[0]), threads=int(info[1]), per_block=int(info[2]), nblocks=int(info[3]))
+
+
+FILTERS_VIT16, FILTERS_WAVE_FAST, FILTERS_WAVE_FAST_PLAIN, FILTERS_CHAIN = 0, 1, 2, 3
+FILTER_RESULT = np.dtype([("bias_d", "<f4"), ("bias_e", "<f4"), ("filtersc", "<f4"), ("vit_fast", "<f4"), ("vit_exact", "<f4"), ("vit_xC", "<i4"),
+                          ("vit_flag", "<u4"), ("route", "<u4"), ("n_vq", "<u4"), ("n_vxq", "<u4"), ("n_fwork", "<u4")])
+
+
+def debug_filters(ctx, profiles, seqs, model, seq, usc, filtersc, mode, nblocks=0):
+    """The bias filter and the Viterbi kernels as the device-driven search runs them on the pairs (model[i], seq[i]) in the given order
+    (include/checkm_hip.h: ckm_debug_filters): (a FILTER_RESULT record array, the cascade's status word)."""
+    model = np.ascontiguousarray(model, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    usc = np.ascontiguousarray(usc, dtype=np.float32)
+    fsc = None if filtersc is None else np.ascontiguousarray(filtersc, dtype=np.float32)
+    assert len(seq) == len(model) == len(usc) and (fsc is None or len(fsc) == len(model))
+    out = np.zeros(len(model), dtype=FILTER_RESULT)
+    status = C.c_uint32(0)
+    _chk(load().ckm_debug_filters(ctx.h, profiles.h, seqs.h, model.ctypes.data, seq.ctypes.data, usc.ctypes.data,
+                                  None if fsc is None else fsc.ctypes.data, len(model), int(mode), int(nblocks), out.ctypes.data, C.byref(status)))
+    return out, int(status.value)
 
 
 def debug_envelopes(ctx, profiles, seqs, model, seq, ienv, jenv):

@@ -187,6 +187,179 @@ extern "C" int ckm_debug_ssv(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_seq
   });
 }
 
+// The filter stages between the MSV stage and Forward the way the device-driven search runs them (ckm_search.hip), on n chosen pairs:
+// bias_filter_kernel, vit16_kernel, vit_kernel<QH, true> and the `decide` epilogues, none of which ckm_debug_stages launches.  A private
+// CascadeDev for ONE group over the worker's cascade tables, every table sized for all n pairs, the search's margins and grids.
+//   VIT16            cand[i] = pair i with the caller's filtersc, the vq of the pairs' one 16-lane class = the caller's order;
+//                    vit16_kernel, then vit_kernel<QH, false> with decide on whatever reached vxq (one launch per class present)
+//   WAVE_FAST        the same with vit_kernel<QH, true> and decide (legal for short models too: their wave-per-pair class)
+//   WAVE_FAST_PLAIN  vit_kernel<QH, true> without decide (out_xC, out_sc, out_flag): the host-driven search's first pass
+//   CHAIN            bias_filter_kernel over the candidate table (the caller's usc; classes may mix), then the FAST and the exact
+//                    Viterbi kernels of every class present, in the search's order
+// Outputs are prefilled with sentinels (all bits set); a queued pair that was not written, a pair reported twice in a queue or as a
+// Forward item, and an entry that is no pair of the call are errors (CKM_EHIP) that name the pair.
+extern "C" int ckm_debug_filters(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_seqs *s, const uint32_t *model, const uint32_t *seq,
+                                 const float *usc, const float *filtersc, uint32_t n, int32_t mode, uint32_t nblocks,
+                                 ckm_filter_result *out, uint32_t *status) {
+  return guarded([&] {
+    if (!ctx_ || !p || !s || !model || !seq || !usc || !out || !status) throw Error(CKM_EINVAL, "NULL argument");
+    if (mode < CKM_FILTERS_VIT16 || mode > CKM_FILTERS_CHAIN) throw Error(CKM_EINVAL, "unknown mode");
+    if (mode != CKM_FILTERS_CHAIN && !filtersc) throw Error(CKM_EINVAL, "NULL argument");
+    if (n == 0 || n > (1u << 22)) throw Error(CKM_EINVAL, "between 1 and 2^22 pairs");
+    if (nblocks > 65536) throw Error(CKM_EINVAL, "at most 65536 workgroups");
+    const uint32_t nb = nblocks ? nblocks : GRID_VIT;
+    bool present[NVC] = {false};
+    std::vector<std::vector<uint32_t>> vq(NVC);
+    unsigned long long ws_need = 0;
+    int q16 = -1;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (model[i] >= p->hmm.size() || seq[i] >= s->nseq) throw Error(CKM_EINVAL, "pair index out of range");
+      if (p->too_long[model[i]]) throw Error(CKM_ERANGE, "model longer than the instantiated kernel classes");
+      if (s->len[seq[i]] <= 0) throw Error(CKM_EINVAL, "empty sequence (the lists of a search hold none)");
+      const DevModel &d = p->dm[model[i]];
+      if (mode == CKM_FILTERS_VIT16) {
+        if (!d.vit16Q) throw Error(CKM_ERANGE, "the model has no 16-lane Viterbi image");
+        if (q16 >= 0 && q16 != d.vit16Q) throw Error(CKM_EINVAL, "the pairs of a VIT16 call must share one 16-lane class");
+        q16 = d.vit16Q;
+      }
+      const int c = (mode == CKM_FILTERS_VIT16 || mode == CKM_FILTERS_CHAIN) ? d.vit_cls : d.vitx_cls;
+      if (c < 0 || c >= NVC || d.vitx_cls < NV16 || d.vitx_cls >= NVC || d.fb_cls < 0 || d.fb_cls >= NFC) throw Error(CKM_ERANGE, "no kernel instance for this model length");
+      present[c] = true; present[d.vitx_cls] = true;
+      if (mode != CKM_FILTERS_CHAIN) vq[c].push_back(i);
+      ws_need += (((unsigned long long)(s->len[seq[i]] + 1) * 6ull) + 31ull) & ~31ull;
+    }
+    ctx_->settle();
+    Worker *ctx = &ctx_->w[0];
+    ctx->plan_key.clear();                 // this entry overwrites the worker's cascade tables
+    HIPCHK(hipSetDevice(ctx->device));
+    const DevModel *dm = p->d_models.as<DevModel>();
+    const LenEntry *lt = s->d_lentab.as<LenEntry>();
+    const uint8_t *res = s->d_res.as<uint8_t>();
+    const uint64_t *off = s->d_off.as<uint64_t>();
+    const int32_t *dlen = s->d_len.as<int32_t>();
+    hipStream_t st = ctx->stream;
+    auto table = [](DevBuf &b, size_t bytes) { b.ensure(std::max<size_t>(64, bytes)); return b.p; };
+    uint32_t *d_cnt = (uint32_t *)table(ctx->c_cnt, 2 * CC_SIZE * 4);
+    unsigned long long *d_tops = (unsigned long long *)table(ctx->c_tops, 4 * 8);
+    CascadeDev cd; memset(&cd, 0, sizeof(cd));
+    cd.cand = (PairRec *)table(ctx->c_cand, (size_t)n * sizeof(PairRec)); cd.cap_cand = n;
+    cd.bias_raw = (float *)table(ctx->c_bias, (size_t)n * 8);
+    cd.vit_fast = (float *)table(ctx->c_vfast, (size_t)n * 4); cd.vit_exact = (float *)table(ctx->c_vexact, (size_t)n * 4);
+    cd.vit_flag = (uint32_t *)table(ctx->c_vflag, (size_t)n * 4); cd.route = (uint8_t *)table(ctx->c_route, n);
+    cd.vq = (uint32_t *)table(ctx->c_vq, (size_t)n * NVC * 4); cd.vxq = (uint32_t *)table(ctx->c_vxq, (size_t)n * NVC * 4); cd.cap_vq = n;
+    cd.fq = (uint32_t *)table(ctx->c_fq, (size_t)n * NFC * 4); cd.cap_fq = n;
+    cd.fwork = (FbWork *)table(ctx->c_fwork, (size_t)n * sizeof(FbWork)); cd.cap_fwork = n;
+    cd.gcnt = d_cnt; cd.cnt = d_cnt + CC_SIZE;
+    cd.ws_top = d_tops; cd.ws_cap = 2 * ws_need;      // (a Forward item only reserves its rows here: nothing of the workspace is touched before Forward)
+    cd.seq_len = dlen;
+    cd.margin_msv = kMarginMsv; cd.margin_vit = kMarginVit; cd.margin_fwd = kMarginFwd;
+    int32_t *d_xC = (int32_t *)table(ctx->vitx, (size_t)n * 4); float *d_sc = (float *)table(ctx->vits, (size_t)n * 4); uint32_t *d_flag = (uint32_t *)table(ctx->vitf, (size_t)n * 4);
+    // candidate table, counters, queues
+    std::vector<PairRec> pr(n);
+    for (uint32_t i = 0; i < n; ++i) { pr[i].model = model[i]; pr[i].seq = seq[i]; pr[i].usc = usc[i]; pr[i].filtersc = mode == CKM_FILTERS_CHAIN ? 0.f : filtersc[i]; }
+    std::vector<uint32_t> cnt(2 * CC_SIZE, 0u);
+    cnt[CC_SIZE + CC_CAND] = n;
+    wcopy(ctx, cd.cand, pr.data(), (size_t)n * sizeof(PairRec), hipMemcpyHostToDevice);
+    for (int c = 0; c < NVC; ++c) if (!vq[c].empty()) {
+      cnt[CC_SIZE + CC_VQ + c] = (uint32_t)vq[c].size();
+      wcopy(ctx, cd.vq + (size_t)c * n, vq[c].data(), vq[c].size() * 4, hipMemcpyHostToDevice);
+    }
+    wcopy(ctx, d_cnt, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice);
+    HIPCHK(hipMemsetAsync(d_tops, 0, 4 * 8, st));
+    auto sentinels = [&] {
+      HIPCHK(hipMemsetAsync(cd.vit_fast, 0xff, (size_t)n * 4, st)); HIPCHK(hipMemsetAsync(cd.vit_exact, 0xff, (size_t)n * 4, st));
+      HIPCHK(hipMemsetAsync(cd.vit_flag, 0xff, (size_t)n * 4, st));
+    };
+    sentinels();
+    HIPCHK(hipMemsetAsync(cd.bias_raw, 0xff, (size_t)n * 8, st));
+    HIPCHK(hipMemsetAsync(cd.route, mode == CKM_FILTERS_CHAIN ? 0xee : 1, n, st));      // (0xee: "the bias filter wrote no route"; 1: what it writes for a pair it queues for the FAST kernel)
+    HIPCHK(hipMemsetAsync(d_xC, 0xff, (size_t)n * 4, st)); HIPCHK(hipMemsetAsync(d_sc, 0xff, (size_t)n * 4, st)); HIPCHK(hipMemsetAsync(d_flag, 0xff, (size_t)n * 4, st));
+    uint32_t *gc = cd.cnt;
+    int rc = 0;
+    auto exact_launches = [&] {
+      for (int c = NVC - 1; c >= NV16; --c) if (present[c])
+        rc |= launch_vit(kVitQH[c - NV16], std::max(64u, GRID_VIT / 4), st, WorkQueue{cd.vxq + (size_t)c * cd.cap_vq, gc + CC_VXQ + c, cd.cap_vq}, cd.cand, dm, lt, res, off, dlen, nullptr, nullptr, nullptr, false, &cd);
+    };
+    if (mode == CKM_FILTERS_CHAIN) {
+      launch_bias_filter(st, GRID_MSV, cd, dm, lt, res, off);
+      sentinels();                         // (the bias filter zeroes the Viterbi outputs of every candidate: "not written" has to be told from a score again)
+    }
+    if (mode == CKM_FILTERS_WAVE_FAST_PLAIN) {
+      for (int c = NVC - 1; c >= NV16; --c) if (present[c])
+        rc |= launch_vit(kVitQH[c - NV16], nb, st, WorkQueue{cd.vq + (size_t)c * cd.cap_vq, gc + CC_VQ + c, cd.cap_vq}, cd.cand, dm, lt, res, off, dlen, d_xC, d_sc, d_flag, true, nullptr);
+    } else {
+      for (int c = NVC - 1; c >= 0; --c) if (present[c]) {
+        const WorkQueue qv{cd.vq + (size_t)c * cd.cap_vq, gc + CC_VQ + c, cd.cap_vq};
+        if (c < NV16) rc |= launch_vit16(kVit16Q[c], nb, st, qv, cd.cand, dm, lt, res, off, dlen, cd);
+        else rc |= launch_vit(kVitQH[c - NV16], nb, st, qv, cd.cand, dm, lt, res, off, dlen, nullptr, nullptr, nullptr, true, &cd);
+      }
+      exact_launches();
+    }
+    if (rc) throw Error(CKM_ERANGE, "no Viterbi kernel instance");
+    HIPCHK(hipGetLastError());
+    // results
+    std::vector<float> raw((size_t)n * 2), vfast(n), vexact(n), psc(n);
+    std::vector<uint32_t> vflag(n), pflag(n), lists_vq((size_t)n * NVC), lists_vxq((size_t)n * NVC);
+    std::vector<int32_t> pxC(n); std::vector<uint8_t> route(n);
+    HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pr.data(), cd.cand, (size_t)n * sizeof(PairRec), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(raw.data(), cd.bias_raw, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(vfast.data(), cd.vit_fast, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(vexact.data(), cd.vit_exact, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(vflag.data(), cd.vit_flag, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(route.data(), cd.route, n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(lists_vq.data(), cd.vq, (size_t)n * NVC * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(lists_vxq.data(), cd.vxq, (size_t)n * NVC * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pxC.data(), d_xC, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(psc.data(), d_sc, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(pflag.data(), d_flag, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    *status = cnt[CC_STATUS];
+    const uint32_t nfw = std::min(cnt[CC_FWORK], n);
+    std::vector<FbWork> fw(nfw);
+    if (nfw) wcopy(ctx, fw.data(), cd.fwork, (size_t)nfw * sizeof(FbWork), hipMemcpyDeviceToHost);
+    auto bits_of = [](float f) { uint32_t u; memcpy(&u, &f, 4); return u; };
+    auto name = [&](uint32_t i) { return "pair " + std::to_string(i) + " (model " + std::to_string(model[i]) + ", sequence " + std::to_string(seq[i]) + ", L = " + std::to_string(s->len[seq[i]]) + ")"; };
+    const bool plain = mode == CKM_FILTERS_WAVE_FAST_PLAIN;
+    for (uint32_t i = 0; i < n; ++i) {
+      ckm_filter_result &o = out[i];
+      o.bias_d = raw[2 * (size_t)i]; o.bias_e = raw[2 * (size_t)i + 1]; o.filtersc = pr[i].filtersc;
+      o.vit_fast = plain ? psc[i] : vfast[i]; o.vit_exact = vexact[i]; o.vit_flag = plain ? pflag[i] : vflag[i];
+      o.vit_xC = plain ? pxC[i] : INT32_MAX; o.route = route[i]; o.n_vq = o.n_vxq = o.n_fwork = 0;
+      if (pr[i].model != model[i] || pr[i].seq != seq[i]) throw Error(CKM_EHIP, "the candidate record of " + name(i) + " was overwritten");
+    }
+    if (cnt[CC_SIZE + CC_CAND] != n) throw Error(CKM_EHIP, "the candidate counter changed");
+    for (int c = 0; c < NVC; ++c) {
+      const uint32_t nv = cnt[CC_SIZE + CC_VQ + c], nx = cnt[CC_SIZE + CC_VXQ + c];
+      if (nv > n || nx > n) throw Error(CKM_EHIP, "queue of class " + std::to_string(c) + " holds " + std::to_string(nv) + " FAST and " + std::to_string(nx) + " exact entries for " + std::to_string(n) + " pairs");
+      if ((nv || nx) && !present[c]) throw Error(CKM_EHIP, "entries in the queue of class " + std::to_string(c) + ", which no pair of the call has");
+      for (uint32_t k = 0; k < nv; ++k) {
+        const uint32_t i = lists_vq[(size_t)c * n + k];
+        if (i >= n) throw Error(CKM_EHIP, "FAST queue of class " + std::to_string(c) + ", position " + std::to_string(k) + ": " + std::to_string(i) + " is no pair of the call");
+        if (p->dm[model[i]].vit_cls != c && !(mode != CKM_FILTERS_CHAIN && p->dm[model[i]].vitx_cls == c)) throw Error(CKM_EHIP, name(i) + " sits in the FAST queue of class " + std::to_string(c));
+        if (out[i].n_vq++) throw Error(CKM_EHIP, name(i) + " sits twice in the FAST queue of class " + std::to_string(c));
+        if (bits_of(out[i].vit_fast) == 0xffffffffu || out[i].vit_flag == 0xffffffffu) throw Error(CKM_EHIP, "FAST queue of class " + std::to_string(c) + ", position " + std::to_string(k) + ": the kernel wrote nothing for " + name(i));
+      }
+      for (uint32_t k = 0; k < nx; ++k) {
+        const uint32_t i = lists_vxq[(size_t)c * n + k];
+        if (i >= n) throw Error(CKM_EHIP, "exact queue of class " + std::to_string(c) + ", position " + std::to_string(k) + ": " + std::to_string(i) + " is no pair of the call");
+        if (p->dm[model[i]].vitx_cls != c) throw Error(CKM_EHIP, name(i) + " sits in the exact queue of class " + std::to_string(c));
+        if (out[i].n_vxq++) throw Error(CKM_EHIP, name(i) + " sits twice in the exact queue of class " + std::to_string(c));
+        if (bits_of(out[i].vit_exact) == 0xffffffffu) throw Error(CKM_EHIP, "exact queue of class " + std::to_string(c) + ", position " + std::to_string(k) + ": the kernel wrote nothing for " + name(i));
+      }
+    }
+    if (cnt[CC_FWORK] > n) throw Error(CKM_EHIP, std::to_string(cnt[CC_FWORK]) + " Forward items for " + std::to_string(n) + " pairs");
+    for (uint32_t t = 0; t < nfw; ++t) {
+      const uint32_t i = fw[t].cand;
+      if (i >= n || fw[t].model != model[i] || fw[t].seq != seq[i]) throw Error(CKM_EHIP, "Forward item " + std::to_string(t) + " is no pair of the call");
+      if (out[i].n_fwork++) throw Error(CKM_EHIP, name(i) + " was handed to Forward twice");
+    }
+    if (mode == CKM_FILTERS_CHAIN) for (uint32_t i = 0; i < n; ++i) {
+      if (out[i].route == 0xee || bits_of(out[i].bias_d) == 0xffffffffu) throw Error(CKM_EHIP, "the bias filter wrote nothing for " + name(i));
+    }
+  });
+}
+
 extern "C" int ckm_debug_envelopes(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_seqs *s, const uint32_t *model, const uint32_t *seq,
                                    const int32_t *ienv, const int32_t *jenv, uint32_t n, ckm_envelope_result *out) {
   return guarded([&] {

@@ -272,6 +272,10 @@ inline int vit_class_id(int QH) { for (int i = 0; i < ckm::NVW; ++i) if (kVitQH[
 inline int vit16_class_id(int Q16) { for (int i = 0; i < ckm::NV16; ++i) if (kVit16Q[i] == Q16) return i; return -1; }
 inline int fb_class_id(int Q) { for (int i = 0; i < ckm::NFC; ++i) if (kFbQ[i] == Q) return i; return -1; }
 
+// the device-driven cascade's constants, shared by the search (ckm_search.hip) and the diagnostics that run its stages (ckm_debug.hip)
+constexpr float kMarginMsv = 0.01f, kMarginVit = 0.01f, kMarginFwd = 0.05f;       // bits: widths of the conservative bands around F1/F2, F2 (Viterbi) and F3
+constexpr uint32_t GRID_FB = 4096, GRID_VIT = 2048, GRID_MSV = 1024;      // workgroups of the persistent chain kernels (other sizes were measured in round 2: no gain)
+
 constexpr int NWORKERS = 8;          // upper bound; CKM_WORKERS (default 3) selects how many a large search uses
 
 struct ckm_ctx {

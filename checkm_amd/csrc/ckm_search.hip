@@ -706,7 +706,7 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   float *d_hens = dev_table<float>(ctx->c_hens, cp.hens);
   cd0.hens_top = d_tops + 1; cd0.hens_cap = cp.hens;
   cd0.seq_len = dlen;
-  cd0.margin_msv = 0.01f; cd0.margin_vit = 0.01f; cd0.margin_fwd = 0.05f;
+  cd0.margin_msv = kMarginMsv; cd0.margin_vit = kMarginVit; cd0.margin_fwd = kMarginFwd;
   cd0.env_inplace = env_inplace() ? 1u : 0u;
   FwdOut *d_fout_f = dev_table<FwdOut>(ctx->c_fout_f, cp.fwork), *d_fout_e = dev_table<FwdOut>(ctx->c_fout_e, cp.ework), *d_fout_r = dev_table<FwdOut>(ctx->c_fout_r, cp.rwork);
   int32_t *d_rerr_e = dev_table<int32_t>(ctx->c_rerr_e, cp.ework);
@@ -732,7 +732,6 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   //  host-driven cascade: 1 SSV + finish, 2 exact MSV, 3 bias filter, 4 Viterbi fast, 5 Viterbi exact, 6 Forward parser, 7 Backward
   //  parser, 8 regions, 9-11 envelope Forward / Backward / OA, 12 region Forward, 13 ensembles)
   const int stop = getenv("CKM_CHAIN_STOP") ? atoi(getenv("CKM_CHAIN_STOP")) : 99;
-  constexpr uint32_t GRID_FB = 4096, GRID_VIT = 2048, GRID_MSV = 1024;      // workgroups of the persistent chain kernels (other sizes were measured in round 2: no gain)
   HIPCHK(hipMemsetAsync(d_gcnt, 0, (NG + 1) * CC_SIZE * sizeof(uint32_t), ms));
   HIPCHK(hipMemsetAsync(d_tops, 0, 4 * sizeof(unsigned long long), ms));
   if (owner->ssv_prev_done) HIPCHK(hipStreamWaitEvent(ms, owner->ssv_prev_done, 0));     // previous lane's SSV launches

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 11
+#define CKM_ABI_VERSION 12
 
 enum {
   CKM_OK      =  0,
@@ -507,6 +507,31 @@ int ckm_debug_stages(ckm_ctx *ctx, const ckm_profiles *p, const ckm_seqs *s,
  * entry: the device reported a pair twice (or in both tables), a pair that was not listed, or no Smax for a pair. */
 int ckm_debug_ssv(ckm_ctx *ctx, const ckm_profiles *p, const ckm_seqs *s, uint32_t model, const uint32_t *seq, uint32_t n,
                   uint32_t per_block, int32_t lanes, uint16_t *smax, uint8_t *route, float *usc, int32_t *info);
+/* The filter stages between MSV and Forward as the device-driven search runs them (ABI 12): the bias filter with its F1/F2 decisions, the
+ * FAST Viterbi kernels (16 lanes per pair, four pairs per wavefront, for models of up to 512 nodes; a wavefront per pair beyond, and for
+ * every model in the host-driven search) and the exact kernel with their F2 decisions, on n pairs (model[i], seq[i]) in the caller's
+ * order; no sequence may be empty.  nblocks: workgroups of the FAST launches (0: what the search uses).
+ *   CKM_FILTERS_VIT16            every pair's model must share ONE 16-lane class; candidate i = pair i with usc[i], filtersc[i]; the FAST queue
+ *                                is the caller's order; then the exact kernel on whatever the FAST kernel queued for it
+ *   CKM_FILTERS_WAVE_FAST        the same with the wave-per-pair FAST kernel (any model)
+ *   CKM_FILTERS_WAVE_FAST_PLAIN  the wave-per-pair FAST kernel without decisions: vit_fast, vit_xC (32767 on overflow), vit_flag only
+ *   CKM_FILTERS_CHAIN            the bias filter over the candidates (usc[i]; filtersc is ignored and may be NULL), then every Viterbi launch of the search
+ * Per pair: bias_d, bias_e (CHAIN: the bias filter's d0 + d1 and power-of-two exponent), filtersc (CHAIN: the approximate null score the
+ * device stored; else the caller's), route (0xff dead, 0 Viterbi skipped, 1 FAST kernel only, 2 exact kernel, | 0x10 exact kernel because the
+ * NEED for the filter was within the margin), vit_fast / vit_exact (all bits set: not written), vit_flag, vit_xC (INT32_MAX where the mode
+ * has none), and how often the pair appears in the FAST queues, the exact queues and as a Forward item.  *status = the cascade's status word.
+ * CKM_EHIP with a message naming the pair: a queued pair that was not written, a pair reported twice, an entry that is no pair of the call. */
+enum { CKM_FILTERS_VIT16 = 0, CKM_FILTERS_WAVE_FAST = 1, CKM_FILTERS_WAVE_FAST_PLAIN = 2, CKM_FILTERS_CHAIN = 3 };
+typedef struct {
+  float    bias_d, bias_e, filtersc;
+  float    vit_fast, vit_exact;
+  int32_t  vit_xC;
+  uint32_t vit_flag, route;
+  uint32_t n_vq, n_vxq, n_fwork;
+} ckm_filter_result;
+int ckm_debug_filters(ckm_ctx *ctx, const ckm_profiles *p, const ckm_seqs *s, const uint32_t *model, const uint32_t *seq,
+                      const float *usc, const float *filtersc, uint32_t n, int32_t mode, uint32_t nblocks,
+                      ckm_filter_result *out, uint32_t *status);
 typedef struct {
   float envsc, oasc, fwd_xC; int32_t nscale; float null2[20];
   int32_t hmm_from, hmm_to, ali_from, ali_to; int32_t ok;

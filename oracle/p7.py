@@ -72,6 +72,9 @@ def lib():
         L.p7o_msv_costs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.p7o_ssv_smax.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.p7o_msv_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.p7o_vit_costs.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.p7o_vit_fast.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.p7o_vit_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
         L.p7o_ensemble_seed.restype = C.c_uint32
         L.p7o_ensemble_seed.argtypes = [C.c_int]
         L.p7o_region_ensemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -101,6 +104,20 @@ def ssv_smax(cost, bias, seqs):
     cat, offs = _concat(seqs)
     out = np.zeros(len(seqs), dtype=np.int32)
     lib().p7o_ssv_smax(cost.ctypes.data, cost.shape[1], int(bias), cat.ctypes.data, offs.ctypes.data, len(seqs), out.ctypes.data)
+    return out
+
+
+def vit_fast(sc, emis, trans, w_move, seqs, with_j=False):
+    """The Viterbi filter in plain clamped integers over emis[29][M] / trans[8][M] and the scalars of HmmSet.vit_costs, w_move[s] per
+    sequence.  Without the J state (xB constant per sequence): the largest match cell of any row.  with_j: the filter's xC (32767 on
+    overflow)."""
+    emis = np.ascontiguousarray(emis, dtype=np.int16)
+    trans = np.ascontiguousarray(trans, dtype=np.int16)
+    w_move = np.ascontiguousarray(w_move, dtype=np.int32)
+    cat, offs = _concat(seqs)
+    out = np.zeros(len(seqs), dtype=np.int32)
+    lib().p7o_vit_fast(emis.ctypes.data, trans.ctypes.data, emis.shape[1], int(sc["base_w"]), int(sc["wE_move"]), int(sc["wE_loop"]), w_move.ctypes.data,
+                       1 if with_j else 0, cat.ctypes.data, offs.ctypes.data, len(seqs), out.ctypes.data)
     return out
 
 
@@ -225,6 +242,32 @@ class HmmSet(object):
         xJ = np.zeros(len(seqs), dtype=np.int32); sc = np.zeros(len(seqs), dtype=np.float32); ok = np.zeros(len(seqs), dtype=np.int32)
         lib().p7o_msv_stage(self.model(i), cat.ctypes.data, offs.ctypes.data, len(seqs), xJ.ctypes.data, sc.ctypes.data, ok.ctypes.data)
         return xJ, sc, ok
+
+    def vit_costs(self, i, lengths):
+        """The word costs of model i's Viterbi filter: ({base_w, wE_move, wE_loop, scale_w}, emis[29][M], trans[8][M] -- BM MM IM DM into
+        node k, MD MI II DD out of it, node k at k - 1 --, w_move per length)."""
+        M = self.M(i)
+        sc = np.zeros(3, dtype=np.int32)
+        scale = C.c_float()
+        emis = np.zeros((29, M), dtype=np.int16)
+        trans = np.zeros((8, M), dtype=np.int16)
+        L = np.ascontiguousarray(lengths, dtype=np.int32)
+        w_move = np.zeros(len(L), dtype=np.int32)
+        lib().p7o_vit_costs(self.model(i), sc.ctypes.data, C.byref(scale), emis.ctypes.data, trans.ctypes.data, L.ctypes.data, len(L), w_move.ctypes.data)
+        return dict(base_w=int(sc[0]), wE_move=int(sc[1]), wE_loop=int(sc[2]), scale_w=np.float32(scale.value)), emis, trans, w_move
+
+    def vit_stage(self, i, seqs):
+        """MSV, bias and exact Viterbi filter of model i against every sequence, unconditionally and without Forward: a dict of arrays
+        msv_sc, bias_sc, vit_xC, vit_sc, pass_bias, pass_vit (as stages() reports them), need_vit (MSV P-value above F2 on the
+        bias-corrected score) and vit_ok (the F2 test of vit_sc against bias_sc by itself)."""
+        cat, offs = _concat(seqs)
+        n = len(seqs)
+        out = dict(msv_sc=np.zeros(n, dtype=np.float32), bias_sc=np.zeros(n, dtype=np.float32), vit_xC=np.zeros(n, dtype=np.int32),
+                   vit_sc=np.zeros(n, dtype=np.float32), pass_bias=np.zeros(n, dtype=np.int32), need_vit=np.zeros(n, dtype=np.int32),
+                   pass_vit=np.zeros(n, dtype=np.int32), vit_ok=np.zeros(n, dtype=np.int32))
+        lib().p7o_vit_stage(self.model(i), cat.ctypes.data, offs.ctypes.data, n, *[out[k].ctypes.data for k in
+                            ("msv_sc", "bias_sc", "vit_xC", "vit_sc", "pass_bias", "need_vit", "pass_vit", "vit_ok")])
+        return out
 
     def format_domtblout(self, rows, names, descs):
         arr = (Row * max(1, len(rows)))(*rows)

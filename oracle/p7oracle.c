@@ -1325,6 +1325,7 @@ static int filters(const PROF *p, const BIASHMM *bh, const uint8_t *dsq, int L, 
     }
   }
   if (!st->pass_vit && !all_stages) return 0;
+  if (all_stages == 2) return 0;     /* the integer filters only (p7o_vit_stage) */
   XF xf; xf_config(p, L, 1, &xf);
   float xCL; int ns;
   fwdsc = forward(p, &xf, dsq, L, NULL, NULL, &xCL, &ns);
@@ -1529,6 +1530,96 @@ int p7o_msv_stage(const P7O_HMM *hmm, const uint8_t *dsq, const int64_t *offsets
     float seq_score = (float)((double)(usc - lc.nullsc) / LOG2C);
     double P = gumbel_surv(seq_score, ev[P7O_MMU], ev[P7O_MLAMBDA]);
     xJ_out[s] = xJ; sc_out[s] = usc; pass_out[s] = !(P > F1);
+  }
+  prof_free(p);
+  return 0;
+}
+
+/* The word costs of the Viterbi filter of one model, for the plain reference of tests/vit_reference.py: scalars = {base_w, wE_move,
+ * wE_loop}, *scale_w, emis[x * M + k - 1] = the emission word of symbol x (0..28) at node k (1..M), trans[t * M + k - 1] with t = 0..7
+ * for BM MM IM DM (into node k) and MD MI II DD (out of node k; -32768 at k = M), w_move[i] = the N/C/J move word at length L[i]. */
+int p7o_vit_costs(const P7O_HMM *hmm, int32_t *scalars, float *scale_w, int16_t *emis, int16_t *trans, const int32_t *L, int nL, int32_t *w_move)
+{
+  PROF *p = prof_create(hmm);
+  const int M = p->M;
+  const int16_t *tw[8] = { p->wBM, p->wMM, p->wIM, p->wDM, p->wMD, p->wMI, p->wII, p->wDD };
+  scalars[0] = p->base_w; scalars[1] = p->wE_move; scalars[2] = p->wE_loop; *scale_w = p->scale_w;
+  for (int x = 0; x < P7O_KP; x++) for (int k = 1; k <= M; k++) emis[(size_t)x * M + k - 1] = p->rwv[x*(M+1)+k];
+  for (int t = 0; t < 8; t++) for (int k = 1; k <= M; k++) trans[(size_t)t * M + k - 1] = tw[t][k];
+  for (int i = 0; i < nL; i++) { LENCFG lc; lencfg(p, L[i], 1, &lc); w_move[i] = lc.w_move; }
+  prof_free(p);
+  return 0;
+}
+
+/* The Viterbi filter in plain integers, from caller-supplied word tables (layout of p7o_vit_costs); every addition of the cell
+ * recurrence is clamped to [-32768, 32767].  with_j = 0: WITHOUT the J state -- xB = base_w + w_move[s] is a constant of the sequence --
+ * and out[s] = xE, the largest match cell of any row (-32768: none).  with_j = 1: the filter itself -- after every row xC = max(xC, xE +
+ * wE_move), xJ = max(xJ, xE + wE_loop), xB = max(xJ, base_w) + w_move[s]; a row with xE >= 32767 ends the sequence -- and out[s] = xC
+ * (32767 on overflow). */
+int p7o_vit_fast(const int16_t *emis, const int16_t *trans, int M, int base_w, int wE_move, int wE_loop, const int32_t *w_move, int with_j,
+                 const uint8_t *dsq, const int64_t *offsets, int nseq, int32_t *out)
+{
+  const int16_t *wBM = trans, *wMM = trans + M, *wIM = trans + 2 * (size_t)M, *wDM = trans + 3 * (size_t)M;
+  const int16_t *wMD = trans + 4 * (size_t)M, *wMI = trans + 5 * (size_t)M, *wII = trans + 6 * (size_t)M, *wDD = trans + 7 * (size_t)M;
+  int32_t *buf = malloc(sizeof(int32_t) * 6 * ((size_t)M + 1));
+  for (int s = 0; s < nseq; s++) {
+    const uint8_t *x = dsq + offsets[s]; const int L = (int)(offsets[s+1] - offsets[s]);
+    int32_t *mm = buf, *im = mm + (M+1), *dm = im + (M+1), *mn = dm + (M+1), *in = mn + (M+1), *dn = in + (M+1);
+    int best = -32768, xB = base_w + w_move[s], xJ = -32768, xC = -32768, overflow = 0;
+    for (int k = 0; k <= M; k++) mm[k] = im[k] = dm[k] = mn[k] = in[k] = dn[k] = -32768;
+    for (int i = 0; i < L; i++) {
+      const int16_t *e = emis + (size_t)x[i] * M;
+      int xE = -32768;
+      for (int k = 1; k <= M; k++) {                   /* cell k of the arrays = node k; word of node k at k - 1 */
+        int sv = sat16(xB + wBM[k-1]), t;
+        t = sat16(mm[k-1] + wMM[k-1]); if (t > sv) sv = t;
+        t = sat16(im[k-1] + wIM[k-1]); if (t > sv) sv = t;
+        t = sat16(dm[k-1] + wDM[k-1]); if (t > sv) sv = t;
+        sv = sat16(sv + e[k-1]);
+        if (sv > xE) xE = sv;
+        mn[k] = sv;
+        int a = sat16(mm[k] + wMI[k-1]), b2 = sat16(im[k] + wII[k-1]);
+        in[k] = a > b2 ? a : b2;
+      }
+      dn[1] = -32768;
+      for (int k = 2; k <= M; k++) {
+        int a = sat16(mn[k-1] + wMD[k-2]), b2 = sat16(dn[k-1] + wDD[k-2]);
+        dn[k] = a > b2 ? a : b2;
+      }
+      if (xE > best) best = xE;
+      if (with_j) {
+        if (xE >= 32767) { overflow = 1; break; }
+        if (xE + wE_move > xC) xC = xE + wE_move;
+        if (xE + wE_loop > xJ) xJ = xE + wE_loop;
+        xB = (xJ > base_w ? xJ : base_w) + w_move[s];
+      }
+      { int32_t *t; t = mm; mm = mn; mn = t; t = im; im = in; in = t; t = dm; dm = dn; dn = t; }
+    }
+    out[s] = with_j ? (overflow ? 32767 : xC) : best;
+  }
+  free(buf);
+  return 0;
+}
+
+/* The filter stages up to the exact Viterbi filter of one model against many sequences, every one of them unconditionally and without
+ * Forward: what p7o_stages reports as msv_sc, bias_sc, vit_xC, vit_sc, pass_bias and pass_vit, plus need_vit (the MSV P-value on the
+ * bias-corrected score is above F2: the pipeline runs the Viterbi filter) and vit_ok (the F2 test of the Viterbi score against bias_sc,
+ * whatever the earlier stages said). */
+int p7o_vit_stage(const P7O_HMM *hmm, const uint8_t *dsq, const int64_t *offsets, int nseq, float *msv_sc, float *bias_sc, int32_t *vit_xC,
+                  float *vit_sc, int32_t *pass_bias, int32_t *need_vit, int32_t *pass_vit, int32_t *vit_ok)
+{
+  PROF *p = prof_create(hmm); BIASHMM bh; bias_setup(hmm, &bh);
+  const float *ev = hmm->evparam;
+  for (int s = 0; s < nseq; s++) {
+    const int L = (int)(offsets[s+1] - offsets[s]);
+    P7O_STAGES st;
+    filters(p, &bh, dsq + offsets[s], L, &st, 2);
+    msv_sc[s] = st.msv_sc; bias_sc[s] = st.bias_sc; vit_xC[s] = st.vit_xC; vit_sc[s] = st.vit_sc;
+    pass_bias[s] = st.pass_bias; pass_vit[s] = st.pass_vit;
+    float seq_score = (float)((double)(st.msv_sc - st.bias_sc) / LOG2C);
+    need_vit[s] = gumbel_surv(seq_score, ev[P7O_MMU], ev[P7O_MLAMBDA]) > F2;
+    seq_score = (float)((double)(st.vit_sc - st.bias_sc) / LOG2C);
+    vit_ok[s] = !(gumbel_surv(seq_score, ev[P7O_VMU], ev[P7O_VLAMBDA]) > F2);
   }
   prof_free(p);
   return 0;

@@ -117,6 +117,17 @@ int p7o_ssv_smax(const uint8_t *cost, int M, int bias, const uint8_t *dsq, const
 /* the MSV stage alone (p7o_stages' msv_xJ, msv_sc, pass_msv) of one model against nseq sequences */
 int p7o_msv_stage(const P7O_HMM *hmm, const uint8_t *dsq, const int64_t *offsets, int nseq, int32_t *xJ, float *sc, int32_t *pass);
 
+/* the word costs of one model's Viterbi filter (tests/vit_reference.py): scalars[3] = base_w, wE_move, wE_loop; emis[29 * M] and
+ * trans[8 * M] (BM MM IM DM into node k, MD MI II DD out of it), node k at k - 1; w_move[i] = the N/C/J move word at length L[i] */
+int p7o_vit_costs(const P7O_HMM *hmm, int32_t *scalars, float *scale_w, int16_t *emis, int16_t *trans, const int32_t *L, int nL, int32_t *w_move);
+/* the Viterbi filter in plain clamped integers over caller-supplied word tables: with_j = 0 without its J state (xB = base_w + w_move[s]
+ * constant per sequence), out[s] = xE, the largest match cell of any row; with_j = 1 the filter itself, out[s] = xC (32767 on overflow) */
+int p7o_vit_fast(const int16_t *emis, const int16_t *trans, int M, int base_w, int wE_move, int wE_loop, const int32_t *w_move, int with_j,
+                 const uint8_t *dsq, const int64_t *offsets, int nseq, int32_t *out);
+/* MSV, bias and exact Viterbi filter of one model against nseq sequences, unconditionally, without Forward */
+int p7o_vit_stage(const P7O_HMM *hmm, const uint8_t *dsq, const int64_t *offsets, int nseq, float *msv_sc, float *bias_sc, int32_t *vit_xC,
+                  float *vit_sc, int32_t *pass_bias, int32_t *need_vit, int32_t *pass_vit, int32_t *vit_ok);
+
 /* canonical-order float DP pieces exposed for kernel unit parity */
 int p7o_envelope(const P7O_HMM *hmm, const uint8_t *dsq, int L_full, int ienv, int jenv,
                  float *envsc, float *oasc, float *null2 /*[20]*/, int32_t *coords /*[4] hmmfrom,hmmto,alifrom,alito*/,

@@ -164,7 +164,7 @@ def test_bin_rows_reads_unmaterialised_bins_from_the_kept_key_ids():
 def test_abi_10_refuses_bad_arguments_without_a_device():
     from checkm_amd import _lib
     lib = _lib.load()
-    assert lib.ckm_abi_version() == 11 == _lib.ABI_VERSION
+    assert lib.ckm_abi_version() == 12 == _lib.ABI_VERSION
     member, hit_sum, n_markers = mc.synthetic(5, 104, seed=1)
     bits = mc.pack(member)
     thr = [5.0, 10.0, 50.0, 20.0]
