@@ -133,6 +133,20 @@ class MergeColumns(C.Structure):
                [(f, C.c_double) for f in ("ms_upload", "ms_bins", "ms_count", "ms_scan", "ms_fill", "ms_download", "ms_write", "ms_total")]
 
 
+class BamHeaderView(C.Structure):
+    _fields_ = [("n_ref", C.c_uint32), ("names", C.POINTER(C.c_char_p)), ("lengths", C.POINTER(C.c_int64)), ("header_bytes", C.c_uint64)]
+
+
+class CoverageParams(C.Structure):
+    _fields_ = [("min_align_per", C.c_double), ("max_edit_dist_per", C.c_double), ("min_qc", C.c_double), ("all_reads", C.c_int32), ("budget_bytes", C.c_uint64)]
+
+
+class CoverageTiming(C.Structure):
+    _fields_ = [("records", C.c_uint64), ("batches", C.c_uint64), ("blocks", C.c_uint64), ("inflated_bytes", C.c_uint64),
+                ("error_reason", C.c_uint32), ("error_record", C.c_uint64), ("error_read", C.c_char * 256)] + \
+               [(f, C.c_double) for f in ("ms_read", "ms_inflate", "ms_offsets", "ms_upload", "ms_kernel", "ms_download", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -164,6 +178,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_seq_genes_read", "ckm_tetra_profile_read", "ckm_tetra_profile_view_get", "ckm_tetra_profile_gather", "ckm_tetra_profile_free",
            "ckm_outliers_run", "ckm_outliers_columns_get", "ckm_outliers_free",
            "ckm_merge_check", "ckm_merge_run", "ckm_merge_columns_get", "ckm_merge_free",
+           "ckm_bam_open", "ckm_bam_header", "ckm_bam_close", "ckm_coverage_check", "ckm_coverage_run",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -257,6 +272,12 @@ def load():
     L.ckm_merge_columns_get.argtypes = [C.c_void_p, C.POINTER(MergeColumns)]
     L.ckm_merge_free.argtypes = [C.c_void_p]
     L.ckm_merge_free.restype = None
+    L.ckm_bam_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.ckm_bam_header.argtypes = [C.c_void_p, C.POINTER(BamHeaderView)]
+    L.ckm_bam_close.argtypes = [C.c_void_p]
+    L.ckm_bam_close.restype = None
+    L.ckm_coverage_check.argtypes = [C.POINTER(CoverageParams)]
+    L.ckm_coverage_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CoverageParams), C.c_void_p, C.POINTER(CoverageTiming)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -969,3 +990,65 @@ def merge_pairs(ctx, member_bits, hit_sum, n_markers, ngenes, thresholds, bin_id
     finally:
         load().ckm_merge_free(h)
     return out
+
+
+COVERAGE_SLOTS = ("reads", "duplicates", "secondary", "failed_qc", "failed_align_len", "failed_edit_dist", "failed_proper_pair", "mapped", "numerator")
+COVERAGE_REASONS = {1: "an auxiliary field runs past the record", 2: "tag 'NM' not present", 3: "tag 'NM' is not an integer", 4: "an auxiliary field of unknown type"}
+
+
+class CoverageRecordError(CkmError):
+    """A record the device pass could not classify: reason (COVERAGE_REASONS), record (ordinal in the file), read (its name)."""
+
+    def __init__(self, code, msg, reason, record, read):
+        CkmError.__init__(self, code, msg)
+        self.reason, self.record, self.read = reason, record, read
+
+
+class Bam(object):
+    """A BAM file opened by the library's host reader (ckm_bam_open: BGZF blocks, header; no device, no index).  Read once."""
+
+    def __init__(self, path):
+        self.path = path
+        self.h = C.c_void_p()
+        _chk(load().ckm_bam_open(os.fsencode(path), C.byref(self.h)))
+        v = BamHeaderView()
+        _chk(load().ckm_bam_header(self.h, C.byref(v)))
+        n = int(v.n_ref)
+        self.references = [v.names[k].decode("utf-8") for k in range(n)]
+        self.lengths = [int(v.lengths[k]) for k in range(n)]
+        self.header_bytes = int(v.header_bytes)
+
+    def close(self):
+        if self.h:
+            load().ckm_bam_close(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _coverage_params(all_reads, min_align_per, max_edit_dist_per, min_qc, budget_bytes):
+    return CoverageParams(float(min_align_per), float(max_edit_dist_per), float(min_qc), 1 if all_reads else 0, int(budget_bytes))
+
+
+def coverage_check(all_reads, min_align_per, max_edit_dist_per, min_qc):
+    """ckm_coverage_check: the parameter tests of coverage_counters(), without a device."""
+    p = _coverage_params(all_reads, min_align_per, max_edit_dist_per, min_qc, 0)
+    _chk(load().ckm_coverage_check(C.byref(p)))
+
+
+def coverage_counters(ctx, bam, all_reads, min_align_per, max_edit_dist_per, min_qc, budget_bytes=0):
+    """The device pass over every record of an open Bam (ckm_coverage_run): ([n_ref, 9] int64 in the order of COVERAGE_SLOTS, timing
+    dict).  Raises CoverageRecordError for a record whose auxiliary fields cannot be walked or whose NM is needed and missing."""
+    p = _coverage_params(all_reads, min_align_per, max_edit_dist_per, min_qc, budget_bytes)
+    out = np.zeros((max(1, len(bam.references)), len(COVERAGE_SLOTS)), dtype=np.int64)
+    t = CoverageTiming()
+    rc = load().ckm_coverage_run(ctx.h, bam.h, C.byref(p), out.ctypes.data, C.byref(t))
+    if rc != 0 and t.error_reason:
+        raise CoverageRecordError(rc, load().ckm_last_error().decode(errors="replace"), int(t.error_reason), int(t.error_record), t.error_read.decode(errors="replace"))
+    _chk(rc)
+    timing = {f: getattr(t, f) for f in ("records", "batches", "blocks", "inflated_bytes", "ms_read", "ms_inflate", "ms_offsets", "ms_upload", "ms_kernel", "ms_download", "ms_total")}
+    return out[:len(bam.references)], timing

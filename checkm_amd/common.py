@@ -79,3 +79,28 @@ def read_fasta(path):
     if name is not None:
         recs.append((name, desc, ''.join(parts)))
     return recs
+
+
+def _centre(text, width):
+    excess = width - len(text)
+    left = excess // 2
+    if excess % 2 and len(text) % 2 == 0:          # the odd blank goes left of a text of even length, right of an odd one
+        left += 1
+    return ' ' * left + text + ' ' * (excess - left)
+
+
+def frame_table(header, rows, sort_col=None, reverse=False):
+    """The framed table of the non-tab output modes (qa, profile), in the layout the reference's table writer produces for the settings
+    it is given there: rules above the header, below it and at the end, no vertical rules, one blank of padding, the first column left,
+    the others centred, floats as %.2f.  sort_col: rows ordered by that column, ties by the whole row (as a decorated sort does)."""
+    rows = list(rows)
+    if sort_col is not None:
+        i = header.index(sort_col)
+        rows.sort(key=lambda r: [r[i]] + list(r), reverse=reverse)
+    cells = [[('%.2f' % v) if isinstance(v, float) else str(v) for v in row] for row in rows]
+    width = [max([len(h)] + [len(r[k]) for r in cells]) for k, h in enumerate(header)]
+    rule = '-' + ''.join('-' * (w + 3) for w in width)
+
+    def line(values):
+        return ' ' + ''.join(' ' + (v.ljust(w) if k == 0 else _centre(v, w)) + '  ' for k, (v, w) in enumerate(zip(values, width)))
+    return '\n'.join([rule, line(header), rule] + [line(r) for r in cells] + [rule])

@@ -11,6 +11,8 @@ class DefaultValues(object):
     LENGTH = 0.7
     PSEUDOGENE_LENGTH = 0.3
 
+    UNBINNED = 'unbinned'          # bin id of a sequence no bin holds (coverage and profile files)
+
     TAXON_MARKER_FILE_HEADER = '# [Taxon Marker File]'
     LINEAGE_MARKER_FILE_HEADER = '# [Lineage Marker File]'
     SEQ_CONCAT_CHAR = '&&'

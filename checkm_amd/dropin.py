@@ -62,3 +62,15 @@ def install():
     else:
         from checkm_amd import merger as mg
         checkm.merger.Merger = mg.Merger
+    # `checkm coverage`, `checkm profile` and `qa --coverage_file`: BAM files read by the library (no pysam), the records on the device
+    try:
+        import checkm.coverage
+        import checkm.profile
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import coverage as cv
+        from checkm_amd import profile as pf
+        checkm.coverage.Coverage = cv.Coverage
+        checkm.coverage.CoverageStruct = cv.CoverageStruct
+        checkm.profile.Profile = pf.Profile

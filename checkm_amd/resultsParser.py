@@ -16,7 +16,7 @@ import numpy as np
 
 from checkm_amd import qa as cqa
 from checkm_amd import runtime
-from checkm_amd.common import checkFileExists
+from checkm_amd.common import checkFileExists, frame_table
 from checkm_amd.defaultValues import DefaultValues
 from checkm_amd.hmmer import HmmerHitDOM, read_domtblout
 from checkm_amd.markerSets import count_sets
@@ -521,7 +521,7 @@ def _marker_hits_from(res, b, keys, row_to_hit, lazy=False):
 
 
 class _Table(object):
-    """Minimal frame-ruled table for the non-tab output mode."""
+    """The rows of the non-tab output mode; drawn by common.frame_table."""
 
     def __init__(self, header):
         self.header = header
@@ -531,18 +531,7 @@ class _Table(object):
         self.rows.append(row)
 
     def render(self, sort_col=None, reverse=False):
-        rows = list(self.rows)
-        if sort_col is not None:
-            i = self.header.index(sort_col)
-            rows.sort(key=lambda r: r[i], reverse=reverse)
-        txt = [[("%.2f" % c) if isinstance(c, float) else str(c) for c in r] for r in rows]
-        w = [max([len(self.header[i])] + [len(r[i]) for r in txt]) for i in range(len(self.header))]
-        rule = '-' * (sum(w) + 2 * len(w) + len(w) - 1)
-        out = [rule, '  '.join((self.header[i].ljust(w[i]) if i == 0 else self.header[i].center(w[i])) for i in range(len(w))), rule]
-        for r in txt:
-            out.append('  '.join((r[i].ljust(w[i]) if i == 0 else r[i].center(w[i])) for i in range(len(w))))
-        out.append(rule)
-        return '\n'.join(out)
+        return frame_table(self.header, self.rows, sort_col, reverse)
 
 
 class ResultsParser(object):
@@ -940,12 +929,13 @@ class ResultsParser(object):
 
     def printSummary(self, outputFormat, aai, binIdToBinMarkerSets, bIndividualMarkers, coverageFile, bTabTable, outFile, anaFolder):
         """The QA table in any of the output formats (resultsParser.py:275-319).  Tab mode is byte-compatible with the reference; the framed
-        table of the non-tab mode (formats 1, 2, 3, 9) is drawn by _Table (prettytable is not a dependency here).
+        table of the non-tab mode (formats 1, 2, 3, 9) is drawn by common.frame_table in the reference's layout (prettytable is not a dependency here).
         One process per GPU: formats 1 and 2 are completed by the single gather of QA rows and printed by rank 0; for the other
         formats rank 0 reads the tables the other ranks wrote."""
+        coverageBinProfiles = None
         if coverageFile:
-            self.logger.error('Coverage profiles are not part of this path.')
-            sys.exit(1)
+            from checkm_amd.coverage import Coverage
+            coverageBinProfiles = Coverage(1).binProfiles(coverageFile)
         from checkm_amd import dist as cdist
         if self._pool is not None:
             if outputFormat in (1, 2):
@@ -967,7 +957,7 @@ class ResultsParser(object):
         if outFile:
             sys.stdout = open(outFile, 'w')
         try:
-            header = self._getHeader(outputFormat, binIdToBinMarkerSets[list(binIdToBinMarkerSets.keys())[0]], None, bTabTable)
+            header = self._getHeader(outputFormat, binIdToBinMarkerSets[list(binIdToBinMarkerSets.keys())[0]], coverageBinProfiles, bTabTable)
             table = None
             if bTabTable or outputFormat not in (1, 2, 3, 9):
                 bTabTable = True
@@ -977,7 +967,7 @@ class ResultsParser(object):
                 table = _Table(header)
             reported = 0
             for binId in sorted(self.results.keys()):
-                reported += self.results[binId].printSummary(outputFormat, aai, binIdToBinMarkerSets[binId], bIndividualMarkers, None, table, anaFolder)
+                reported += self.results[binId].printSummary(outputFormat, aai, binIdToBinMarkerSets[binId], bIndividualMarkers, coverageBinProfiles, table, anaFolder)
             if outputFormat in (6, 7) and reported == 0:
                 print('[No marker genes satisfied the reporting criteria.]')
             if not bTabTable:

@@ -489,6 +489,43 @@ int  ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, const uint64_t
 int  ckm_merge_columns_get(const ckm_merge *r, ckm_merge_columns *out);
 void ckm_merge_free(ckm_merge *r);
 
+/* ---- `checkm coverage`: BAM records on the device (additions to ABI 12; no existing entry point changes) ---------------------------------
+ * Replaces pysam and the per-read Python loop of Coverage.__workerThread (checkm/coverage.py:186-239).  ckm_bam_open walks the BGZF
+ * blocks and parses the BAM header on the host; no device is needed for open / header / close.  ckm_coverage_run inflates the
+ * file in batches of whole records (budget_bytes of inflated bytes, 0: CKM_COVERAGE_BATCH_MB, default 256, << 20; the batches never
+ * change the result), classifies every record on the device by the chain of coverage.py:209-230 (checkm_amd/csrc/coverage_dev.h) and
+ * adds it to its reference's row of out_counters[n_ref][9], all int64: reads, duplicates, secondary or supplementary, failed QC,
+ * failed alignment length, failed edit distance, not properly paired, mapped, and the sum of query_alignment_length over the mapped
+ * reads.  Records with refID -1 count nowhere.  A handle is read once: a second run on it sees no records.
+ * Refused with CKM_EINVAL and a message that names the file and the record's ordinal: bad magic, a truncated block, a failed inflate,
+ * a record shorter than its fixed part or running past its buffer, n_ref or a refID out of range, the placeholder of a long CIGAR
+ * (real CIGAR in a CG tag: not supported), an auxiliary walk that leaves its record, and an NM tag that is needed and absent or not
+ * an integer.  For the last group timing->error_reason is 1 (walk left the record), 2 (NM absent), 3 (NM not an integer) or 4
+ * (unknown field type), error_record the ordinal and error_read the read's name.  ckm_coverage_check: the tests of the parameters
+ * (no NaN), without a device. */
+typedef struct ckm_bam ckm_bam;
+typedef struct {
+  uint32_t           n_ref;
+  const char *const *names;                 /* [n_ref] */
+  const int64_t     *lengths;               /* [n_ref] */
+  uint64_t           header_bytes;          /* inflated bytes in front of the first record */
+} ckm_bam_header_view;
+typedef struct {
+  double   min_align_per, max_edit_dist_per, min_qc;
+  int32_t  all_reads;
+  uint64_t budget_bytes;
+} ckm_coverage_params;
+typedef struct {
+  uint64_t records, batches, blocks, inflated_bytes;
+  uint32_t error_reason; uint64_t error_record; char error_read[256];
+  double   ms_read, ms_inflate, ms_offsets, ms_upload, ms_kernel, ms_download, ms_total;   /* read, inflate, offsets, total: wall; the others: HIP events */
+} ckm_coverage_timing;
+int  ckm_bam_open(const char *path, ckm_bam **out);
+int  ckm_bam_header(const ckm_bam *b, ckm_bam_header_view *out);
+void ckm_bam_close(ckm_bam *b);
+int  ckm_coverage_check(const ckm_coverage_params *params);
+int  ckm_coverage_run(ckm_ctx *ctx, ckm_bam *b, const ckm_coverage_params *params, int64_t *out_counters, ckm_coverage_timing *timing);
+
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
   int32_t msv_xJ;  float msv_sc, null_sc, bias_sc;
