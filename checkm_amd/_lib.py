@@ -147,6 +147,14 @@ class CoverageTiming(C.Structure):
                [(f, C.c_double) for f in ("ms_read", "ms_inflate", "ms_offsets", "ms_upload", "ms_kernel", "ms_download", "ms_total")]
 
 
+class CoverageWindowsParams(C.Structure):
+    _fields_ = [("min_align_per", C.c_double), ("max_edit_dist_per", C.c_double), ("all_reads", C.c_int32), ("window_size", C.c_int64), ("budget_bytes", C.c_uint64)]
+
+
+class CoverageWindowsTiming(C.Structure):
+    _fields_ = CoverageTiming._fields_ + [("ms_scan", C.c_double), ("slots", C.c_uint64)]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -179,6 +187,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_outliers_run", "ckm_outliers_columns_get", "ckm_outliers_free",
            "ckm_merge_check", "ckm_merge_run", "ckm_merge_columns_get", "ckm_merge_free",
            "ckm_bam_open", "ckm_bam_header", "ckm_bam_close", "ckm_coverage_check", "ckm_coverage_run",
+           "ckm_coverage_windows_check", "ckm_coverage_windows_layout", "ckm_coverage_windows_run",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -278,6 +287,9 @@ def load():
     L.ckm_bam_close.restype = None
     L.ckm_coverage_check.argtypes = [C.POINTER(CoverageParams)]
     L.ckm_coverage_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CoverageParams), C.c_void_p, C.POINTER(CoverageTiming)]
+    L.ckm_coverage_windows_check.argtypes = [C.POINTER(CoverageWindowsParams)]
+    L.ckm_coverage_windows_layout.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.ckm_coverage_windows_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CoverageWindowsParams), C.c_void_p, C.c_void_p, C.POINTER(CoverageWindowsTiming)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -993,7 +1005,9 @@ def merge_pairs(ctx, member_bits, hit_sum, n_markers, ngenes, thresholds, bin_id
 
 
 COVERAGE_SLOTS = ("reads", "duplicates", "secondary", "failed_qc", "failed_align_len", "failed_edit_dist", "failed_proper_pair", "mapped", "numerator")
-COVERAGE_REASONS = {1: "an auxiliary field runs past the record", 2: "tag 'NM' not present", 3: "tag 'NM' is not an integer", 4: "an auxiliary field of unknown type"}
+COVERAGE_REASONS = {1: "an auxiliary field runs past the record", 2: "tag 'NM' not present", 3: "tag 'NM' is not an integer", 4: "an auxiliary field of unknown type",
+                    5: "the read has no CIGAR", 6: "a mapped read starts before its reference"}          # (5 and 6: coverage_windows only)
+COVWIN_SCAN_BLOCK = 1024          # slots per workgroup of the scan over the windows (covwin_dev.h: SCAN_BLOCK)
 
 
 class CoverageRecordError(CkmError):
@@ -1052,3 +1066,41 @@ def coverage_counters(ctx, bam, all_reads, min_align_per, max_edit_dist_per, min
     _chk(rc)
     timing = {f: getattr(t, f) for f in ("records", "batches", "blocks", "inflated_bytes", "ms_read", "ms_inflate", "ms_offsets", "ms_upload", "ms_kernel", "ms_download", "ms_total")}
     return out[:len(bam.references)], timing
+
+
+def _coverage_windows_params(all_reads, min_align_per, max_edit_dist_per, window_size, budget_bytes):
+    w = int(window_size)
+    return CoverageWindowsParams(float(min_align_per), float(max_edit_dist_per), 1 if all_reads else 0, max(-1, min(w, 1 << 62)), int(budget_bytes))
+
+
+def coverage_windows_check(all_reads, min_align_per, max_edit_dist_per, window_size):
+    """ckm_coverage_windows_check: the parameter tests of coverage_windows(), without a device."""
+    p = _coverage_windows_params(all_reads, min_align_per, max_edit_dist_per, window_size, 0)
+    _chk(load().ckm_coverage_windows_check(C.byref(p)))
+
+
+def coverage_windows_layout(bam, window_size):
+    """ckm_coverage_windows_layout: [n_ref + 1] int64, the first slot of every reference and the number of slots; reference k has
+    (L - 1) // w + 1 slots for L > 0 -- its reported windows and the tail."""
+    first = np.zeros(len(bam.references) + 1, dtype=np.int64)
+    _chk(load().ckm_coverage_windows_layout(bam.h, max(-1, min(int(window_size), 1 << 62)), first.ctypes.data))
+    return first
+
+
+def coverage_windows(ctx, bam, all_reads, min_align_per, max_edit_dist_per, window_size, budget_bytes=0):
+    """The device pass of CoverageWindows over every record of an open Bam (ckm_coverage_windows_run): ([n_ref, 9] int64 counters by the
+    chain of coverageWindows.py, [n_ref + 1] first slots, [slots] int64 depth sums, timing dict).  Raises CoverageRecordError as
+    coverage_counters() does, with reasons 5 (no CIGAR) and 6 (mapped read with pos < 0) besides."""
+    p = _coverage_windows_params(all_reads, min_align_per, max_edit_dist_per, window_size, budget_bytes)
+    _chk(load().ckm_coverage_windows_check(C.byref(p)))
+    first = coverage_windows_layout(bam, window_size)
+    out = np.zeros((max(1, len(bam.references)), len(COVERAGE_SLOTS)), dtype=np.int64)
+    sums = np.zeros(max(1, int(first[-1])), dtype=np.int64)
+    t = CoverageWindowsTiming()
+    rc = load().ckm_coverage_windows_run(ctx.h, bam.h, C.byref(p), out.ctypes.data, sums.ctypes.data, C.byref(t))
+    if rc != 0 and t.error_reason:
+        raise CoverageRecordError(rc, load().ckm_last_error().decode(errors="replace"), int(t.error_reason), int(t.error_record), t.error_read.decode(errors="replace"))
+    _chk(rc)
+    timing = {f: getattr(t, f) for f in ("records", "batches", "blocks", "inflated_bytes", "slots", "ms_read", "ms_inflate", "ms_offsets", "ms_upload", "ms_kernel", "ms_scan",
+                                         "ms_download", "ms_total")}
+    return out[:len(bam.references)], first, sums[:int(first[-1])], timing

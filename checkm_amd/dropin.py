@@ -74,3 +74,12 @@ def install():
         checkm.coverage.Coverage = cv.Coverage
         checkm.coverage.CoverageStruct = cv.CoverageStruct
         checkm.profile.Profile = pf.Profile
+    # `checkm gc_bias_plot`: the per-window coverage of a BAM file on the device (the plot class stays the reference's)
+    try:
+        import checkm.coverageWindows
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import coverageWindows as cw
+        checkm.coverageWindows.CoverageWindows = cw.CoverageWindows
+        checkm.coverageWindows.CoverageStruct = cw.CoverageStruct

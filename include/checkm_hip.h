@@ -526,6 +526,40 @@ void ckm_bam_close(ckm_bam *b);
 int  ckm_coverage_check(const ckm_coverage_params *params);
 int  ckm_coverage_run(ckm_ctx *ctx, ckm_bam *b, const ckm_coverage_params *params, int64_t *out_counters, ckm_coverage_timing *timing);
 
+/* ---- CoverageWindows of `checkm gc_bias_plot`: per-window read coverage of a BAM on the device (additions to ABI 12) ---------------------
+ * Replaces pysam, the float64 depth array per reference and the per-read Python loop of checkm/coverageWindows.py.  The chain is that
+ * file's (lines 55-79), NOT the one of ckm_coverage_run: unmapped, duplicate, secondary (0x100 only), QC-fail (0x200 only, no mapping
+ * quality), alen < min_align_per * rlen, NM > max_edit_dist_per * rlen, not a proper pair, mapped -- with rlen = l_seq and alen = the
+ * reference span of the CIGAR (M, D, N, = and X).  A mapped read adds 1 to the depth of [pos, min(pos + alen, L)).
+ * With w = window_size a reference of length L > 0 has (L - 1) / w + 1 slots: window k = [k w, (k + 1) w) for every k with (k + 1) w < L --
+ * the windows the reference reports -- and one last slot with the rest (a window that ends exactly at L is that last slot).
+ * ckm_coverage_windows_layout: out_first[k] = the first slot of reference k, out_first[n_ref] = all slots (n_ref + 1 values); more than
+ * 2^31 - 1 slots: CKM_EINVAL.  ckm_coverage_windows_run reads the file in the batches of ckm_coverage_run (same budget rule) and gives
+ *   out_counters[n_ref][9]   reads, classes 1..7 by this chain, and the numerator: the bases covered by mapped reads after clipping
+ *                            to [0, L), which is the sum of the reference's slots
+ *   out_window_sums[slots]   the sum of the depth over each slot (int64; the caller divides by w, or the numerator by L)
+ * A read costs O(1) memory operations whatever alen / w is (checkm_amd/csrc/covwin_dev.h); a scan after the last batch forms the sums.
+ * Refusals as for ckm_coverage_run, with two more values of error_reason: 5 (a read without CIGAR reaches the alignment-length test: the
+ * reference fails there with a TypeError) and 6 (a mapped read with pos < 0: numpy would wrap the slice; not imitated).
+ * ckm_coverage_windows_check: no NaN fraction, 1 <= window_size <= 2^31 - 1; without a device.  A handle is read once. */
+typedef struct {
+  double   min_align_per, max_edit_dist_per;
+  int32_t  all_reads;
+  int64_t  window_size;
+  uint64_t budget_bytes;
+} ckm_coverage_windows_params;
+typedef struct {
+  uint64_t records, batches, blocks, inflated_bytes;
+  uint32_t error_reason; uint64_t error_record; char error_read[256];
+  double   ms_read, ms_inflate, ms_offsets, ms_upload, ms_kernel, ms_download, ms_total;   /* as ckm_coverage_timing */
+  double   ms_scan;                         /* the scan over the slots (HIP events) */
+  uint64_t slots;                           /* out_first[n_ref] */
+} ckm_coverage_windows_timing;
+int  ckm_coverage_windows_check(const ckm_coverage_windows_params *params);
+int  ckm_coverage_windows_layout(const ckm_bam *b, int64_t window_size, int64_t *out_first);
+int  ckm_coverage_windows_run(ckm_ctx *ctx, ckm_bam *b, const ckm_coverage_windows_params *params, int64_t *out_counters, int64_t *out_window_sums,
+                              ckm_coverage_windows_timing *timing);
+
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
   int32_t msv_xJ;  float msv_sc, null_sc, bias_sc;
