@@ -155,6 +155,11 @@ class CoverageWindowsTiming(C.Structure):
     _fields_ = CoverageTiming._fields_ + [("ms_scan", C.c_double), ("slots", C.c_uint64)]
 
 
+class SeqWindowsTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("windows", "pieces", "batches", "bytes", "skipped_seqs")] + \
+               [(f, C.c_double) for f in ("ms_upload", "ms_count", "ms_td", "ms_download", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -188,6 +193,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_merge_check", "ckm_merge_run", "ckm_merge_columns_get", "ckm_merge_free",
            "ckm_bam_open", "ckm_bam_header", "ckm_bam_close", "ckm_coverage_check", "ckm_coverage_run",
            "ckm_coverage_windows_check", "ckm_coverage_windows_layout", "ckm_coverage_windows_run",
+           "ckm_seq_windows_layout", "ckm_seq_windows_run", "ckm_seq_windows_coding",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -290,6 +296,10 @@ def load():
     L.ckm_coverage_windows_check.argtypes = [C.POINTER(CoverageWindowsParams)]
     L.ckm_coverage_windows_layout.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     L.ckm_coverage_windows_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CoverageWindowsParams), C.c_void_p, C.c_void_p, C.POINTER(CoverageWindowsTiming)]
+    L.ckm_seq_windows_layout.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.ckm_seq_windows_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.POINTER(SeqWindowsTiming)]
+    L.ckm_seq_windows_coding.argtypes = [C.POINTER(C.c_char_p), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1104,3 +1114,59 @@ def coverage_windows(ctx, bam, all_reads, min_align_per, max_edit_dist_per, wind
     timing = {f: getattr(t, f) for f in ("records", "batches", "blocks", "inflated_bytes", "slots", "ms_read", "ms_inflate", "ms_offsets", "ms_upload", "ms_kernel", "ms_scan",
                                          "ms_download", "ms_total")}
     return out[:len(bam.references)], first, sums[:int(first[-1])], timing
+
+
+def seq_windows_layout(seqs, window_size):
+    """first [nseq + 1] int64: the first window of every sequence of a NucSeqs batch and their number (ckm_seq_windows_layout):
+    (L - 1) // window_size windows for a sequence of L > 0 code points.  O(sequences): the library counted the code points when it
+    read the batch.  No device needed."""
+    first = np.zeros(seqs.nseq + 1, dtype=np.int64)
+    _chk(load().ckm_seq_windows_layout(seqs.h, int(window_size), first.ctypes.data))
+    return first
+
+
+def seq_lengths(seqs):
+    """len(seq) of every sequence of a NucSeqs batch in code points, without decoding it: a sequence of L > 0 has L - 1 windows of one."""
+    try:
+        return [int(d) + (1 if n else 0) for d, n in zip(np.diff(seq_windows_layout(seqs, 1)).tolist(), seqs.seq_bytes.tolist())]
+    except CkmError:                                       # more than 2^31 - 1 code points in the batch
+        return [len(seqs.seq(i).decode('utf-8')) for i in range(seqs.nseq)]
+
+
+def seq_windows(ctx, seqs, window_size, bin_sig=None, want_tetra=False, piece_bytes=0, budget_bytes=0):
+    """The device pass over the windows of a NucSeqs batch (ckm_seq_windows_run).  bin_sig: [nfiles, 136] float64 or None.  Returns a
+    dict: first [nseq + 1], base [nwin, 4] uint32 (A, C, G, T+U), seq [nseq, 4] uint64, td [nwin] float64 or None, tetra [nwin, 136]
+    uint32 or None, skipped [nseq] bool (non-ASCII sequences, left to the caller), and the timings."""
+    first = seq_windows_layout(seqs, window_size)
+    nwin, nseq = int(first[-1]), seqs.nseq
+    base = np.zeros((max(1, nwin), 4), dtype=np.uint32)
+    per_seq = np.zeros((max(1, nseq), 4), dtype=np.uint64)
+    skipped = np.zeros(max(1, nseq), dtype=np.uint8)
+    td = tetra = sig = None
+    if bin_sig is not None:
+        sig = np.ascontiguousarray(bin_sig, dtype=np.float64)
+        if sig.shape != (seqs.nfiles, 136):
+            raise ValueError("bin_sig must be [nfiles, 136]")
+        td = np.zeros(max(1, nwin), dtype=np.float64)
+    if want_tetra:
+        tetra = np.zeros((max(1, nwin), 136), dtype=np.uint32)
+    t = SeqWindowsTiming()
+    _chk(load().ckm_seq_windows_run(ctx.h, seqs.h, int(window_size), 1 if (sig is not None or want_tetra) else 0, sig.ctypes.data if sig is not None else None,
+                                    int(piece_bytes), int(budget_bytes), base.ctypes.data, per_seq.ctypes.data, td.ctypes.data if td is not None else None,
+                                    tetra.ctypes.data if tetra is not None else None, skipped.ctypes.data, C.byref(t)))
+    out = dict(first=first, base=base[:nwin], seq=per_seq[:nseq], td=None if td is None else td[:nwin], tetra=None if tetra is None else tetra[:nwin],
+               skipped=skipped[:nseq].astype(bool))
+    out.update((f, getattr(t, f)) for f, _ in SeqWindowsTiming._fields_)
+    return out
+
+
+def seq_windows_coding(seqs, gff_paths, window_size):
+    """(coding bases per window [nwin] int64, missing [nfiles] bool) from bins/<binId>/genes.gff of every file (ckm_seq_windows_coding):
+    np.sum(codingBaseMask[k w:(k + 1) w]); -1 for the windows of a file without a GFF.  No device needed."""
+    n = seqs.nfiles
+    first = seq_windows_layout(seqs, window_size)
+    g = (C.c_char_p * max(1, n))(*[os.fsencode(p) for p in gff_paths])
+    coding = np.zeros(max(1, int(first[-1])), dtype=np.int64)
+    missing = np.zeros(max(1, n), dtype=np.uint8)
+    _chk(load().ckm_seq_windows_coding(g, seqs.h, int(window_size), coding.ctypes.data, missing.ctypes.data))
+    return coding[:int(first[-1])], missing[:n].astype(bool)

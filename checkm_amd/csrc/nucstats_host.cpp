@@ -16,6 +16,7 @@
 #include <vector>
 #include "ckm_internal.h"
 #include "nucstats_host.h"
+#include "seqwin_dev.h"
 
 namespace ckm {
 
@@ -167,19 +168,28 @@ static int parse_gff(const char *gff, std::unordered_map<std::string, GffSeq> &s
   return CKM_OK;
 }
 
-// ProdigalGeneFeatureParser.codingBases(seqId): bases of one sequence inside the union of its genes, clipped to [0, last coding base)
-static long long coding_bases(const GffSeq &g) {
+// The coding-base mask of one sequence (ProdigalGeneFeatureParser._buildCodingBaseMask) as disjoint ascending intervals [lo, hi): the
+// union of its genes, clipped to [0, last coding base)
+static void merged_intervals(const GffSeq &g, std::vector<std::pair<long long, long long>> &out) {
   std::vector<std::pair<long long, long long>> iv;
   for (auto &x : g.genes) if (x.second.second > x.second.first - 1) iv.push_back({x.second.first - 1, x.second.second});
   std::sort(iv.begin(), iv.end());
   const long long last = g.last;
-  long long total = 0, cs = 0, ce = -1; bool open = false;
-  auto flush = [&] { if (open) { const long long lo = std::max(cs, 0LL), hi = std::min(ce, last); if (hi > lo) total += hi - lo; } };
+  long long cs = 0, ce = -1; bool open = false;
+  auto flush = [&] { if (open) { const long long lo = std::max(cs, 0LL), hi = std::min(ce, last); if (hi > lo) out.push_back({lo, hi}); } };
   for (auto &v : iv) {
     if (open && v.first <= ce) ce = std::max(ce, v.second);
     else { flush(); cs = v.first; ce = v.second; open = true; }
   }
   flush();
+}
+
+// ProdigalGeneFeatureParser.codingBases(seqId): bases of one sequence inside the union of its genes
+static long long coding_bases(const GffSeq &g) {
+  std::vector<std::pair<long long, long long>> iv;
+  merged_intervals(g, iv);
+  long long total = 0;
+  for (auto &v : iv) total += v.second - v.first;
   return total;
 }
 
@@ -250,6 +260,8 @@ extern "C" int ckm_nucseq_read(const char *const *paths, uint32_t nfiles, ckm_nu
       }
     }
     for (auto &s : B->ids) B->id_ptr.push_back(s.c_str());
+    B->seq_cp.assign(B->seq_off.size(), 0);
+    for_each_parallel((uint32_t)B->seq_off.size(), [&](uint32_t s) { B->seq_cp[s] = sw::code_points(B->text.data(), B->seq_off[s], B->seq_bytes[s]); });
     *out = B.release();
     return CKM_OK;
   } catch (const Error &e) { set_last_error(e.what()); return e.code; }
@@ -307,4 +319,72 @@ extern "C" int ckm_bin_genes_read(const char *const *gff_paths, const char *cons
   for (uint32_t k = 0; k < nb; ++k)
     if (rc[k]) { set_last_error(err[k]); return rc[k]; }
   return CKM_OK;
+}
+
+// ---- the windows of the plot commands (seqwin_dev.h) ----------------------------------------------------------------------------------
+namespace ckm {
+void window_layout(const ckm_nucseq *b, uint64_t w, std::vector<uint64_t> &first) {
+  if (!sw::window_layout(b->seq_cp.data(), (uint32_t)b->seq_cp.size(), w, first))
+    throw Error(CKM_ERANGE, "more than 2^31 - 1 windows in one call: use a larger window or fewer files");
+}
+}  // namespace ckm
+
+extern "C" int ckm_seq_windows_layout(const ckm_nucseq *b, int64_t window_size, int64_t *out_first) {
+  try {
+    if (!b || !out_first) throw Error(CKM_EINVAL, "NULL argument");
+    if (window_size < 1 || (uint64_t)window_size > sw::MAX_WINDOWS) throw Error(CKM_EINVAL, "window_size must be between 1 and 2^31 - 1");
+    std::vector<uint64_t> first;
+    window_layout(b, (uint64_t)window_size, first);
+    for (size_t k = 0; k < first.size(); ++k) out_first[k] = (int64_t)first[k];
+    return CKM_OK;
+  } catch (const Error &e) { set_last_error(e.what()); return e.code; }
+  catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  catch (const std::exception &e) { set_last_error(e.what()); return CKM_EINVAL; }
+}
+
+// np.sum(mask[k w : (k + 1) w]) for every window of every sequence: the merged intervals against the window bounds, O(intervals + windows)
+extern "C" int ckm_seq_windows_coding(const char *const *gff_paths, const ckm_nucseq *b, int64_t window_size, int64_t *out_coding, uint8_t *missing) {
+  try {
+    if (!gff_paths || !b || !out_coding || !missing) throw Error(CKM_EINVAL, "NULL argument");
+    if (window_size < 1 || (uint64_t)window_size > sw::MAX_WINDOWS) throw Error(CKM_EINVAL, "window_size must be between 1 and 2^31 - 1");
+    const long long w = (long long)window_size;
+    std::vector<uint64_t> first;
+    window_layout(b, (uint64_t)w, first);
+    const uint32_t nb = (uint32_t)b->file_first.size() - 1;
+    std::vector<int> rc(nb, CKM_OK);
+    std::vector<std::string> err(nb);
+    for_each_parallel(nb, [&](uint32_t k) {
+      try {
+        if (!gff_paths[k]) { rc[k] = CKM_EINVAL; err[k] = "NULL path"; return; }
+        std::unordered_map<std::string, GffSeq> seqs;
+        bool have_table = false, miss = false; long tt = 0;
+        rc[k] = parse_gff(gff_paths[k], seqs, have_table, tt, miss, err[k]);
+        missing[k] = miss ? 1 : 0;
+        if (rc[k]) return;
+        std::vector<std::pair<long long, long long>> iv;
+        for (uint32_t s = b->file_first[k]; s < b->file_first[k + 1]; ++s) {
+          const long long nw = (long long)(first[s + 1] - first[s]);
+          int64_t *out = out_coding + first[s];
+          for (long long x = 0; x < nw; ++x) out[x] = miss ? -1 : 0;
+          if (miss || !nw) continue;
+          auto it = seqs.find(b->ids[s]);
+          if (it == seqs.end()) continue;
+          iv.clear();
+          merged_intervals(it->second, iv);
+          for (auto &v : iv) {
+            if (v.first / w >= nw) break;                      // ascending: nothing behind it reaches a window either
+            const long long z = std::min((v.second - 1) / w, nw - 1);
+            for (long long x = v.first / w; x <= z; ++x)
+              out[x] += std::min(v.second, (x + 1) * w) - std::max(v.first, x * w);
+          }
+        }
+      } catch (const std::bad_alloc &) { rc[k] = CKM_ENOMEM; err[k] = "out of host memory"; }
+      catch (const std::exception &e) { rc[k] = CKM_EINVAL; err[k] = e.what(); }
+    });
+    for (uint32_t k = 0; k < nb; ++k)
+      if (rc[k]) { set_last_error(err[k]); return rc[k]; }
+    return CKM_OK;
+  } catch (const Error &e) { set_last_error(e.what()); return e.code; }
+  catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  catch (const std::exception &e) { set_last_error(e.what()); return CKM_EINVAL; }
 }

@@ -34,7 +34,13 @@ struct NucFile {                       // one FASTA file as readFasta leaves it:
 struct ckm_nucseq {
   std::vector<char> text;              // sequences at 16-byte boundaries, zero padded, 64 bytes of slack at the end
   std::vector<uint64_t> seq_off, seq_bytes;
+  std::vector<uint64_t> seq_cp;        // code points of every sequence (len(seq) of the Python str), counted once when the batch is read
   std::vector<uint32_t> file_first;
   std::vector<std::string> ids;
   std::vector<const char *> id_ptr;
 };
+
+namespace ckm {
+// first window of every sequence of a batch for windows of w, from b->seq_cp (seqwin_dev.h); CKM_ERANGE beyond 2^31 - 1 windows
+void window_layout(const ckm_nucseq *b, uint64_t w, std::vector<uint64_t> &first);
+}  // namespace ckm

@@ -83,3 +83,20 @@ def install():
         from checkm_amd import coverageWindows as cw
         checkm.coverageWindows.CoverageWindows = cw.CoverageWindows
         checkm.coverageWindows.CoverageStruct = cw.CoverageStruct
+    # `checkm gc_plot`, `coding_plot`, `tetra_plot`, `dist_plot` and the FASTA half of `gc_bias_plot`: the plot classes stay the reference's
+    # and compute inline, so the names their modules imported are bound to the library's answers (checkm_amd/plotHooks.py)
+    try:
+        import checkm.plot.codingDensityPlots
+        import checkm.plot.gcBiasPlots
+        import checkm.plot.gcPlots
+        import checkm.plot.tetraDistPlots
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import plotHooks as ph
+        for mod in (checkm.plot.gcPlots, checkm.plot.gcBiasPlots, checkm.plot.codingDensityPlots):
+            mod.readFasta = ph.readFasta
+            mod.baseCount = ph.baseCount
+        checkm.plot.codingDensityPlots.ProdigalGeneFeatureParser = ph.ProdigalGeneFeatureParser
+        checkm.plot.tetraDistPlots.readFasta = ph.readFasta
+        checkm.plot.tetraDistPlots.GenomicSignatures = ph.GenomicSignatures

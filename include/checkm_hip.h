@@ -560,6 +560,38 @@ int  ckm_coverage_windows_layout(const ckm_bam *b, int64_t window_size, int64_t 
 int  ckm_coverage_windows_run(ckm_ctx *ctx, ckm_bam *b, const ckm_coverage_windows_params *params, int64_t *out_counters, int64_t *out_window_sums,
                               ckm_coverage_windows_timing *timing);
 
+/* ---- SequenceWindows of the plot commands: per-window GC, coding density and tetranucleotide distance (additions to ABI 12) ------------
+ * Replaces the per-window loops of checkm/plot/gcPlots.py:55-75, gcBiasPlots.py:51-66, codingDensityPlots.py:73-89 and
+ * tetraDistPlots.py:63-79 over the sequences of a ckm_nucseq batch.  With w = window_size (1 .. 2^31 - 1), window k = [k w, (k + 1) w)
+ * of a sequence of L code points exists while (k + 1) w < L: (L - 1) / w windows for L > 0, none that ends at L, no tail.
+ * ckm_seq_windows_layout: out_first[s] = the first window of sequence s, out_first[nseq] = all windows (nseq + 1 values); more than
+ * 2^31 - 1 windows: CKM_ERANGE.  No device needed.
+ * ckm_seq_windows_run, on the device (checkm_amd/csrc/seqwin_dev.h, kernels_seqwin.hip):
+ *   out_base_counts[nwin][4]  A, C, G, T+U of every window after upper-casing (baseCount)
+ *   out_seq_counts[nseq][4]   the same over every whole sequence
+ *   out_td[nwin]              tetra != 0 and bin_sig != NULL: np.sum(np.abs(sig - bin_sig[file])) with sig_i = count_i / total over the
+ *                             136 canonical 4-mers whose four bytes lie inside the window (A/C/G/T either case; a 4-mer across a window
+ *                             seam belongs to no window), in the summation order of ckm_outliers_run's TD; nan for a window without one.
+ *                             bin_sig: [nfiles * 136], BinTools.binTetraSig of every file
+ *   out_tetra_counts[nwin][136]  optional (tetra != 0): the counts themselves; CKM_ERANGE when they do not fit the budget
+ *   out_skipped[nseq]         1: the sequence holds non-ASCII bytes (its bytes are not its code points) and was not sent to the device;
+ *                             its rows are zero (nan) and the caller computes them
+ * piece_bytes: bytes of a window per wavefront (0 = 4096; 16 .. 1 MiB).  budget_bytes: the 544-byte count rows of a batch of windows
+ * (0: CKM_NUCSTATS_BATCH_MB, default 1024, << 20); the batches never change the result.  Integer counts, a fixed float64 order:
+ * identical from run to run.
+ * ckm_seq_windows_coding: out_coding[x] = np.sum(codingBaseMask[k w : (k + 1) w]) of window x (checkm/prodigal.py:250-273), from the
+ * parsing of ckm_seq_genes_read: 0 for an id without genes, -1 (and missing[f] = 1) for the windows of a file whose GFF does not
+ * exist.  Host threads, a file per thread; no device needed. */
+typedef struct {
+  uint64_t windows, pieces, batches, bytes, skipped_seqs;
+  double   ms_upload, ms_count, ms_td, ms_download, ms_total;   /* HIP events: copies in, count kernel, td kernel, copies out; wall of the call */
+} ckm_seq_windows_timing;
+int  ckm_seq_windows_layout(const ckm_nucseq *b, int64_t window_size, int64_t *out_first /* [nseq + 1] */);
+int  ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t window_size, int tetra, const double *bin_sig, uint32_t piece_bytes, uint64_t budget_bytes,
+                         uint32_t *out_base_counts, uint64_t *out_seq_counts, double *out_td, uint32_t *out_tetra_counts, uint8_t *out_skipped,
+                         ckm_seq_windows_timing *timing);
+int  ckm_seq_windows_coding(const char *const *gff_paths, const ckm_nucseq *b, int64_t window_size, int64_t *out_coding /* [nwin] */, uint8_t *missing /* [nfiles] */);
+
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
   int32_t msv_xJ;  float msv_sc, null_sc, bias_sc;
