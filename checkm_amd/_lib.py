@@ -160,6 +160,11 @@ class SeqWindowsTiming(C.Structure):
                [(f, C.c_double) for f in ("ms_upload", "ms_count", "ms_td", "ms_download", "ms_total")]
 
 
+class RefDistTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("windows", "blocks", "batches", "bytes")] + \
+               [(f, C.c_double) for f in ("ms_scaffold", "ms_upload", "ms_blocks", "ms_scan", "ms_windows", "ms_download", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -194,6 +199,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_bam_open", "ckm_bam_header", "ckm_bam_close", "ckm_coverage_check", "ckm_coverage_run",
            "ckm_coverage_windows_check", "ckm_coverage_windows_layout", "ckm_coverage_windows_run",
            "ckm_seq_windows_layout", "ckm_seq_windows_run", "ckm_seq_windows_coding",
+           "ckm_refdist_check", "ckm_refdist_run", "ckm_refdist_coding",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -300,6 +306,10 @@ def load():
     L.ckm_seq_windows_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.POINTER(SeqWindowsTiming)]
     L.ckm_seq_windows_coding.argtypes = [C.POINTER(C.c_char_p), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.ckm_refdist_check.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
+    L.ckm_refdist_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.POINTER(RefDistTiming)]
+    L.ckm_refdist_coding.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int64)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1170,3 +1180,46 @@ def seq_windows_coding(seqs, gff_paths, window_size):
     missing = np.zeros(max(1, n), dtype=np.uint8)
     _chk(load().ckm_seq_windows_coding(g, seqs.h, int(window_size), coding.ctypes.data, missing.ctypes.data))
     return coding[:int(first[-1])], missing[:n].astype(bool)
+
+
+REFDIST_STATS = {"gc": 0, "cd": 1, "td": 2}
+
+
+def _refdist_windows(starts, sizes):
+    a, w = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(sizes, dtype=np.int64)
+    if a.ndim != 1 or a.shape != w.shape:
+        raise ValueError("starts and sizes must be two lists of one length")
+    return a, w
+
+
+def refdist_check(stat, sep_len, block, scaffold_len, starts, sizes):
+    """Raises CkmError for arguments ckm_refdist_run would refuse (ckm_refdist_check).  No device needed."""
+    a, w = _refdist_windows(starts, sizes)
+    _chk(load().ckm_refdist_check(int(stat), int(sep_len), int(block), int(scaffold_len), a.ctypes.data, w.ctypes.data, len(a)))
+
+
+def refdist(ctx, seqs, stat, sep_len, starts, sizes, block=0, budget_bytes=0):
+    """The device pass over windows [start, start + size) of the scaffold of a NucSeqs batch (ckm_refdist_run).  stat: 'gc', 'cd' or
+    'td'.  Returns a dict: counts [nwin, 2] uint32 (gc, at) or None, td [nwin] float64 or None, totals [138] uint64 (gc, at, the 136
+    canonical 4-mer counts of the scaffold), and the timings."""
+    a, w = _refdist_windows(starts, sizes)
+    n, code = len(a), REFDIST_STATS[stat]
+    counts = np.zeros((max(1, n), 2), dtype=np.uint32) if code != 2 else None
+    td = np.zeros(max(1, n), dtype=np.float64) if code == 2 else None
+    totals = np.zeros(138, dtype=np.uint64)
+    t = RefDistTiming()
+    _chk(load().ckm_refdist_run(ctx.h, seqs.h, code, int(sep_len), int(block), a.ctypes.data, w.ctypes.data, n, int(budget_bytes),
+                                counts.ctypes.data if counts is not None else None, td.ctypes.data if td is not None else None, totals.ctypes.data, C.byref(t)))
+    out = dict(counts=None if counts is None else counts[:n], td=None if td is None else td[:n], totals=totals)
+    out.update((f, getattr(t, f)) for f, _ in RefDistTiming._fields_)
+    return out
+
+
+def refdist_coding(gff_path, seq_id, starts, sizes):
+    """(coding bases per window [nwin] int64, coding bases of the sequence) of sequence seq_id of a GFF (ckm_refdist_coding):
+    ProdigalGeneFeatureParser.codingBases(seqId, start, start + size) and codingBases(seqId).  No device needed."""
+    a, w = _refdist_windows(starts, sizes)
+    coding = np.zeros(max(1, len(a)), dtype=np.int64)
+    total = C.c_int64()
+    _chk(load().ckm_refdist_coding(os.fsencode(gff_path), seq_id.encode("utf-8"), a.ctypes.data, w.ctypes.data, len(a), coding.ctypes.data, C.byref(total)))
+    return coding[:len(a)], int(total.value)

@@ -3,7 +3,8 @@
 // logic is sw::lane_step (seqwin_dev.h), shared with the host executor of the CPU tests; the distance is ol::td_running / ol::td_combine
 // (outlier_dev.h), the summation of outliers_td_kernel.
 //
-//   seqwin_count_kernel  a wavefront per piece (four per block).  A window starts at any byte, so the wave walks 16-byte-ALIGNED spans
+//   seqwin_count_kernel  a wavefront per piece (four per block), the loop sw::wave_piece (seqwin_wave.h, shared with kernels_refdist.hip).
+//                        A window starts at any byte, so the wave walks 16-byte-ALIGNED spans
 //                        of 1 KiB from the chunk that holds its piece's first byte: every lane loads one aligned 128-bit word (1 KiB per
 //                        instruction, consecutive lanes at consecutive 16-byte chunks) and
 //                        masks the bytes in front of and behind its piece; the three bytes a 4-mer needs behind a chunk come from the
@@ -17,15 +18,10 @@
 #include <cstdint>
 #include "outlier_dev.h"
 #include "seqwin_dev.h"
+#include "seqwin_wave.h"
 
 namespace ckm {
 using namespace sw;
-
-__device__ __forceinline__ uint32_t sw_wave_sum(uint32_t x) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s);
-  return x;
-}
 
 __global__ __launch_bounds__(256) void seqwin_count_kernel(const uint8_t *__restrict__ text, const Piece *__restrict__ pieces, uint32_t npieces,
                                                             const uint8_t *__restrict__ canon, uint32_t *__restrict__ cnt, uint32_t *__restrict__ tet) {
@@ -41,36 +37,11 @@ __global__ __launch_bounds__(256) void seqwin_count_kernel(const uint8_t *__rest
   if (active) P = pieces[t];
   const bool kmers = tet != nullptr && P.tet_row != NO_ROW;
   uint32_t acc[4] = {0, 0, 0, 0};
-  const uint64_t pend = P.start + P.len;
-  for (uint64_t step = P.start & ~(uint64_t)(LANE_BYTES - 1); active && step < pend; step += WAVE_BYTES) {
-    const LaneGeom g = lane_geom(P, step, lane);
-    // every sequence starts at a 16-byte boundary of the text and the text ends in 64 bytes of slack: an aligned word that holds a byte
-    // of the piece or its halo lies inside the buffer
-    uint4 v = make_uint4(0, 0, 0, 0);
-    if (g.load) v = *reinterpret_cast<const uint4 *>(text + g.base);
-    uint32_t h = __shfl_down(v.x, 1);
-    if (lane == WAVE - 1) h = g.kend > LANE_BYTES ? *reinterpret_cast<const uint32_t *>(text + g.base + LANE_BYTES) : 0u;
-    const uint32_t w[5] = {v.x, v.y, v.z, v.w, h};
-    uint8_t b[LANE_BYTES + HALO];
-#pragma unroll
-    for (int k = 0; k < LANE_BYTES + HALO; ++k) b[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-    Lane o;
-    lane_step(b, g.first, g.end, g.kend, o);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[k] += o.cnt[k];
-    if (kmers) {
-      uint32_t m = o.kmer_mask;
-      while (m) {
-        const int j = __builtin_ctz(m);
-        m &= m - 1;
-        atomicAdd(&hist[wv][lcanon[o.code[j]]], 1u);
-      }
-    }
-  }
+  if (active) wave_piece(text, P, lane, kmers, lcanon, hist[wv], acc);
   __syncthreads();
   if (!active) return;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) acc[k] = sw_wave_sum(acc[k]);
+  for (int k = 0; k < 4; ++k) acc[k] = wave_sum(acc[k]);
   const bool alone = (P.flags & 4u) != 0;
   if (lane == 0) {
     uint32_t *row = cnt + (uint64_t)P.cnt_row * 4;

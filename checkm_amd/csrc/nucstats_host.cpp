@@ -17,6 +17,7 @@
 #include "ckm_internal.h"
 #include "nucstats_host.h"
 #include "seqwin_dev.h"
+#include "refdist_dev.h"
 
 namespace ckm {
 
@@ -383,6 +384,51 @@ extern "C" int ckm_seq_windows_coding(const char *const *gff_paths, const ckm_nu
     });
     for (uint32_t k = 0; k < nb; ++k)
       if (rc[k]) { set_last_error(err[k]); return rc[k]; }
+    return CKM_OK;
+  } catch (const Error &e) { set_last_error(e.what()); return e.code; }
+  catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  catch (const std::exception &e) { set_last_error(e.what()); return CKM_EINVAL; }
+}
+
+// ---- the windows of the reference distributions (refdist_dev.h) --------------------------------------------------------------------------
+extern "C" int ckm_refdist_check(int stat, uint32_t sep_len, uint32_t block, uint64_t scaffold_len, const int64_t *starts, const int64_t *sizes, uint64_t nwin) {
+  try {
+    const std::string refusal = rd::check_args(stat, sep_len, block, scaffold_len, starts, sizes, nwin);
+    if (!refusal.empty()) throw Error(rd::refusal_code(scaffold_len, nwin), refusal);
+    return CKM_OK;
+  } catch (const Error &e) { set_last_error(e.what()); return e.code; }
+  catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  catch (const std::exception &e) { set_last_error(e.what()); return CKM_EINVAL; }
+}
+
+// np.sum(mask[start : start + size]) for windows anywhere in one sequence: the merged intervals and the coding bases in front of each,
+// a binary search per window end
+extern "C" int ckm_refdist_coding(const char *gff_path, const char *seq_id, const int64_t *starts, const int64_t *sizes, uint64_t nwin, int64_t *out_coding,
+                                  int64_t *out_total) {
+  try {
+    if (!gff_path || !seq_id || !out_total || (nwin && (!starts || !sizes || !out_coding))) throw Error(CKM_EINVAL, "NULL argument");
+    std::unordered_map<std::string, GffSeq> seqs;
+    bool have_table = false, miss = false; long tt = 0;
+    std::string err;
+    const int rc = parse_gff(gff_path, seqs, have_table, tt, miss, err);
+    if (rc) throw Error(rc, err);
+    if (miss) throw Error(CKM_EIO, std::string("cannot read ") + gff_path);
+    std::vector<std::pair<long long, long long>> iv;
+    auto it = seqs.find(seq_id);
+    if (it != seqs.end()) merged_intervals(it->second, iv);
+    std::vector<long long> before(iv.size() + 1, 0);          // coding bases in front of interval k
+    for (size_t k = 0; k < iv.size(); ++k) before[k + 1] = before[k] + (iv[k].second - iv[k].first);
+    // coding bases in [0, p)
+    auto upto = [&](long long p) {
+      const size_t k = (size_t)(std::upper_bound(iv.begin(), iv.end(), std::make_pair(p, (long long)0x7FFFFFFFFFFFFFFFLL)) - iv.begin());   // intervals with first <= p
+      if (k == 0) return 0LL;
+      return before[k - 1] + (std::min(p, iv[k - 1].second) - iv[k - 1].first);
+    };
+    for (uint64_t x = 0; x < nwin; ++x) {
+      if (starts[x] < 0 || sizes[x] < 0 || sizes[x] > 0x7FFFFFFFFFFFFFFFLL - starts[x]) throw Error(CKM_EINVAL, "window " + std::to_string(x) + " is no range of a sequence");
+      out_coding[x] = (int64_t)(upto(starts[x] + sizes[x]) - upto(starts[x]));
+    }
+    *out_total = (int64_t)before[iv.size()];
     return CKM_OK;
   } catch (const Error &e) { set_last_error(e.what()); return e.code; }
   catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }

@@ -592,6 +592,34 @@ int  ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t window_size,
                          ckm_seq_windows_timing *timing);
 int  ckm_seq_windows_coding(const char *const *gff_paths, const ckm_nucseq *b, int64_t window_size, int64_t *out_coding /* [nwin] */, uint8_t *missing /* [nfiles] */);
 
+/* ---- ReferenceDistributions: the windows behind gc_dist / cd_dist / td_dist (additions to ABI 12) -----------------------------
+ * Replaces the sampling loops of CheckM's scripts/distributionDeltaGC.py, distributionDeltaCodingDensity.py and
+ * distributionDeltaTetraDiff.py.  The sequences of the batch are joined in file order with sep_len 'N' between them (GC 0, TD 4, CD 10)
+ * into one scaffold of L bytes; window x is [starts[x], starts[x] + sizes[x]) of it, anywhere, overlapping freely.
+ * stat: 0 gc, 1 cd (both: the two class counters), 2 td.  block: positions per prefix checkpoint (0 = 256; 16 .. 2^20); the result does
+ * not depend on it.
+ * ckm_refdist_check: CKM_EINVAL with a message for a stat, sep_len (> 1024) or block out of range and for a window with a size below 1
+ * or not inside [0, scaffold_len]; CKM_ERANGE for a scaffold of 2^31 - 1 bytes or more and for more than 2^31 - 1 windows.  No device needed.
+ * ckm_refdist_run, on the device (checkm_amd/csrc/refdist_dev.h, kernels_refdist.hip), after the same checks:
+ *   out_counts[nwin][2]   stat 0 / 1: bytes of the window that are C or G, and that are A, T or U, after upper-casing
+ *   out_td[nwin]          stat 2: np.sum(np.abs(genomeSig - sig)) with sig_i = count_i / total over the canonical 4-mers whose four bytes
+ *                         lie inside the window (A/C/G/T either case), in the summation order of ckm_outliers_run's TD; nan without one
+ *   out_totals[138]       the scaffold's gc, at (stat 0 / 1) and its 136 canonical 4-mer counts (stat 2: genomeSig_i = count_i / sum)
+ * A sequence with non-ASCII bytes: CKM_EINVAL (the caller computes such a genome).  budget_bytes: the 544-byte count rows of a batch of
+ * TD windows (0: CKM_NUCSTATS_BATCH_MB, default 1024, << 20); the batches never change the result.
+ * ckm_refdist_coding: out_coding[x] = np.sum(codingBaseMask[starts[x] : starts[x] + sizes[x]]) of sequence seq_id of the GFF
+ * (ProdigalGeneFeatureParser.codingBases(seqId, start, end), checkm/prodigal.py:250-273) and *out_total = codingBases(seqId), from the
+ * parsing of ckm_seq_genes_read; 0 for an id without genes.  CKM_EIO when the file does not exist.  No device needed. */
+typedef struct {
+  uint64_t windows, blocks, batches, bytes;
+  double   ms_scaffold, ms_upload, ms_blocks, ms_scan, ms_windows, ms_download, ms_total;   /* host join; HIP events; wall of the call */
+} ckm_refdist_timing;
+int  ckm_refdist_check(int stat, uint32_t sep_len, uint32_t block, uint64_t scaffold_len, const int64_t *starts, const int64_t *sizes, uint64_t nwin);
+int  ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint32_t sep_len, uint32_t block, const int64_t *starts, const int64_t *sizes, uint64_t nwin,
+                     uint64_t budget_bytes, uint32_t *out_counts, double *out_td, uint64_t *out_totals, ckm_refdist_timing *timing);
+int  ckm_refdist_coding(const char *gff_path, const char *seq_id, const int64_t *starts, const int64_t *sizes, uint64_t nwin, int64_t *out_coding /* [nwin] */,
+                        int64_t *out_total);
+
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
   int32_t msv_xJ;  float msv_sc, null_sc, bias_sc;
