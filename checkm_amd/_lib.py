@@ -165,6 +165,20 @@ class RefDistTiming(C.Structure):
                [(f, C.c_double) for f in ("ms_scaffold", "ms_upload", "ms_blocks", "ms_scan", "ms_windows", "ms_download", "ms_total")]
 
 
+class FastaIdsView(C.Structure):
+    _fields_ = [("seq_ids", C.POINTER(C.c_char_p)), ("seq_bytes", C.POINTER(C.c_uint64)), ("seq_cp", C.POINTER(C.c_uint64)), ("file_first", C.POINTER(C.c_uint32)),
+                ("nseq", C.c_uint32), ("nfiles", C.c_uint32)]
+
+
+class UnbinnedTotals(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("binned_ids", "binned_bases", "all_seqs", "all_bases", "unbinned_seqs", "unbinned_bases")]
+
+
+class UnbinnedTiming(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("kept", "tiles", "batches", "bytes")] + \
+               [(f, C.c_double) for f in ("ms_stage", "ms_upload", "ms_count", "ms_sum", "ms_download", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -200,6 +214,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_coverage_windows_check", "ckm_coverage_windows_layout", "ckm_coverage_windows_run",
            "ckm_seq_windows_layout", "ckm_seq_windows_run", "ckm_seq_windows_coding",
            "ckm_refdist_check", "ckm_refdist_run", "ckm_refdist_coding",
+           "ckm_fasta_ids_read", "ckm_fasta_ids_view_get", "ckm_fasta_ids_free", "ckm_unbinned_select", "ckm_unbinned_count", "ckm_unbinned_write",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -310,6 +325,13 @@ def load():
     L.ckm_refdist_run.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(RefDistTiming)]
     L.ckm_refdist_coding.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int64)]
+    L.ckm_fasta_ids_read.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.POINTER(C.c_void_p)]
+    L.ckm_fasta_ids_view_get.argtypes = [C.c_void_p, C.POINTER(FastaIdsView)]
+    L.ckm_fasta_ids_free.argtypes = [C.c_void_p]
+    L.ckm_fasta_ids_free.restype = None
+    L.ckm_unbinned_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(UnbinnedTotals)]
+    L.ckm_unbinned_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(UnbinnedTiming)]
+    L.ckm_unbinned_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int64)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1223,3 +1245,71 @@ def refdist_coding(gff_path, seq_id, starts, sizes):
     total = C.c_int64()
     _chk(load().ckm_refdist_coding(os.fsencode(gff_path), seq_id.encode("utf-8"), a.ctypes.data, w.ctypes.data, len(a), coding.ctypes.data, C.byref(total)))
     return coding[:len(a)], int(total.value)
+
+
+class FastaIds(object):
+    """The ids and lengths of FASTA files by the rules of NucSeqs, without their text (ckm_fasta_ids_read); stays in the library until
+    close().  seq_bytes, seq_cp: bytes and code points of every sequence; file_first [nfiles + 1]."""
+
+    def __init__(self, paths):
+        arr = (C.c_char_p * max(1, len(paths)))(*[os.fsencode(p) for p in paths])
+        self.h = C.c_void_p()
+        _chk(load().ckm_fasta_ids_read(arr, len(paths), C.byref(self.h)))
+        v = FastaIdsView()
+        _chk(load().ckm_fasta_ids_view_get(self.h, C.byref(v)))
+        self.nseq, self.nfiles = int(v.nseq), int(v.nfiles)
+        arr = np.ctypeslib.as_array
+        self.seq_bytes = arr(v.seq_bytes, shape=(self.nseq,)).copy() if self.nseq else np.zeros(0, dtype=np.uint64)
+        self.seq_cp = arr(v.seq_cp, shape=(self.nseq,)).copy() if self.nseq else np.zeros(0, dtype=np.uint64)
+        self.file_first = arr(v.file_first, shape=(self.nfiles + 1,)).copy()
+        self._view = v
+
+    def ids(self):
+        return [self._view.seq_ids[i].decode("utf-8") for i in range(self.nseq)]
+
+    def close(self):
+        if self.h:
+            load().ckm_fasta_ids_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def unbinned_select(bins, seqs, min_len):
+    """(keep [nseq] uint8, totals dict) of an assembly read as NucSeqs against the ids of `bins` (a FastaIds, or None): keep = the id is
+    in no bin and the sequence has at least min_len code points (ckm_unbinned_select).  seqs = None: the totals of the bins alone and
+    no keep.  No device needed."""
+    nseq = seqs.nseq if seqs is not None else 0
+    keep = np.zeros(max(1, nseq), dtype=np.uint8)
+    t = UnbinnedTotals()
+    _chk(load().ckm_unbinned_select(bins.h if bins is not None else None, seqs.h if seqs is not None else None, int(min_len), keep.ctypes.data, C.byref(t)))
+    return (keep[:nseq] if seqs is not None else None), dict((f, int(getattr(t, f))) for f, _ in UnbinnedTotals._fields_)
+
+
+def unbinned_count(ctx, seqs, keep, tile_bytes=0, budget_bytes=0):
+    """The device count over the kept sequences of a NucSeqs batch (ckm_unbinned_count).  Returns a dict: counts [nseq, 5] uint64 (A, C,
+    G, T+U, code points; zeros where keep is 0) and the timings."""
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    assert keep.shape == (seqs.nseq,)
+    counts = np.zeros((max(1, seqs.nseq), 5), dtype=np.uint64)
+    t = UnbinnedTiming()
+    _chk(load().ckm_unbinned_count(ctx.h, seqs.h, keep.ctypes.data if seqs.nseq else counts.ctypes.data, int(tile_bytes), int(budget_bytes), counts.ctypes.data, C.byref(t)))
+    out = dict(counts=counts[:seqs.nseq])
+    out.update((f, getattr(t, f)) for f, _ in UnbinnedTiming._fields_)
+    return out
+
+
+def unbinned_write(seqs, keep, counts, seq_path, stats_path):
+    """The two files of Unbinned.run written by the library from the batch's own buffers (ckm_unbinned_write).  Returns the index of the
+    kept sequence without A, C, G, T or U at which the writing stopped (its FASTA record written, its row not), or -1."""
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    assert keep.shape == (seqs.nseq,) and counts.shape == (seqs.nseq, 5)
+    zero = C.c_int64(-1)
+    _chk(load().ckm_unbinned_write(seqs.h, keep.ctypes.data if seqs.nseq else None, counts.ctypes.data if seqs.nseq else None, os.fsencode(seq_path),
+                                   os.fsencode(stats_path), C.byref(zero)))
+    return int(zero.value)

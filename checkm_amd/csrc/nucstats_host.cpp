@@ -78,8 +78,9 @@ static bool py_space(const unsigned char *p, int *len) {
          cp == 0x205F || cp == 0x3000;
 }
 
-// line i..e (without its terminator) of a file opened in text mode
-static void parse_nuc_fasta(const char *path, NucFile &o) {
+// line i..e (without its terminator) of a file opened in text mode.  keep_text = false (ckm_fasta_ids_read): the same rules, but of a
+// sequence only its bytes and code points are kept (o.nbytes, o.ncp), never its text.
+static void parse_nuc_fasta(const char *path, NucFile &o, bool keep_text = true) {
   std::string buf;
   if (!read_bytes(path, buf, o.err)) { o.err_code = CKM_EIO; return; }
   const size_t bad = utf8_invalid_at(buf);
@@ -107,13 +108,16 @@ static void parse_nuc_fasta(const char *path, NucFile &o) {
         std::string id((const char *)p + a, z - a);
         auto it = index.find(id);
         if (it == index.end()) {                               // a repeated id keeps its place and takes the later record
-          index.emplace(id, (uint32_t)o.ids.size()); cur = (long)o.ids.size(); o.ids.push_back(std::move(id)); o.seqs.emplace_back();
-        } else { cur = (long)it->second; o.seqs[cur].clear(); }
+          index.emplace(id, (uint32_t)o.ids.size()); cur = (long)o.ids.size(); o.ids.push_back(std::move(id));
+          if (keep_text) o.seqs.emplace_back(); else { o.nbytes.push_back(0); o.ncp.push_back(0); }
+        } else if (keep_text) { cur = (long)it->second; o.seqs[cur].clear(); }
+        else { cur = (long)it->second; o.nbytes[cur] = 0; o.ncp[cur] = 0; }
       } else {
         if (cur < 0) { o.err_code = CKM_EFORMAT; o.err = std::string("sequence text before the first header in ") + path; return; }
         size_t z = e;                                          // line[0:-1]: the terminator, or the last character of the file
         if (!term) { do { --z; } while (z > i && (p[z] & 0xC0) == 0x80); }
-        o.seqs[cur].append((const char *)p + i, z - i);
+        if (keep_text) o.seqs[cur].append((const char *)p + i, z - i);
+        else { o.nbytes[cur] += z - i; o.ncp[cur] += sw::code_points((const char *)p, i, z - i); }
       }
     }
     i = next;
@@ -269,6 +273,44 @@ extern "C" int ckm_nucseq_read(const char *const *paths, uint32_t nfiles, ckm_nu
   catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
   catch (const std::exception &e) { set_last_error(e.what()); return CKM_EINVAL; }
 }
+
+// The ids and lengths of FASTA files by the rules of ckm_nucseq_read, without their text: a file per thread, each file's buffer freed
+// when its thread is done with it.
+extern "C" int ckm_fasta_ids_read(const char *const *paths, uint32_t nfiles, ckm_fasta_ids **out) {
+  try {
+    if (!out || (nfiles && !paths)) throw Error(CKM_EINVAL, "NULL argument");
+    *out = nullptr;
+    std::vector<NucFile> files(nfiles);
+    for_each_parallel(nfiles, [&](uint32_t b) {
+      if (!paths[b]) { files[b].err_code = CKM_EINVAL; files[b].err = "NULL path"; return; }
+      try { parse_nuc_fasta(paths[b], files[b], false); }
+      catch (const std::exception &e) { files[b].err_code = CKM_ENOMEM; files[b].err = e.what(); }
+    });
+    std::unique_ptr<ckm_fasta_ids> B(new ckm_fasta_ids);
+    B->file_first.push_back(0);
+    for (auto &f : files) {
+      if (f.err_code) throw Error(f.err_code, f.err);
+      for (size_t s = 0; s < f.ids.size(); ++s) {
+        B->ids.push_back(std::move(f.ids[s])); B->seq_bytes.push_back(f.nbytes[s]); B->seq_cp.push_back(f.ncp[s]);
+      }
+      B->file_first.push_back((uint32_t)B->ids.size());
+    }
+    for (auto &s : B->ids) B->id_ptr.push_back(s.c_str());
+    *out = B.release();
+    return CKM_OK;
+  } catch (const Error &e) { set_last_error(e.what()); return e.code; }
+  catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  catch (const std::exception &e) { set_last_error(e.what()); return CKM_EINVAL; }
+}
+
+extern "C" int ckm_fasta_ids_view_get(const ckm_fasta_ids *b, ckm_fasta_ids_view *o) {
+  if (!b || !o) { set_last_error("NULL argument"); return CKM_EINVAL; }
+  o->seq_ids = b->id_ptr.data(); o->seq_bytes = b->seq_bytes.data(); o->seq_cp = b->seq_cp.data(); o->file_first = b->file_first.data();
+  o->nseq = (uint32_t)b->ids.size(); o->nfiles = (uint32_t)b->file_first.size() - 1;
+  return CKM_OK;
+}
+
+extern "C" void ckm_fasta_ids_free(ckm_fasta_ids *b) { delete b; }
 
 extern "C" int ckm_nucseq_view_get(const ckm_nucseq *b, ckm_nucseq_view *o) {
   if (!b || !o) { set_last_error("NULL argument"); return CKM_EINVAL; }

@@ -26,6 +26,7 @@ inline void for_each_parallel(uint32_t n, F &&f) {
 
 struct NucFile {                       // one FASTA file as readFasta leaves it: ids in first-seen order, the last record's sequence
   std::vector<std::string> ids, seqs;
+  std::vector<uint64_t> nbytes, ncp;   // read without text (ckm_fasta_ids_read): bytes and code points per id instead of seqs
   int err_code = 0;
   std::string err;
 };
@@ -35,6 +36,13 @@ struct ckm_nucseq {
   std::vector<char> text;              // sequences at 16-byte boundaries, zero padded, 64 bytes of slack at the end
   std::vector<uint64_t> seq_off, seq_bytes;
   std::vector<uint64_t> seq_cp;        // code points of every sequence (len(seq) of the Python str), counted once when the batch is read
+  std::vector<uint32_t> file_first;
+  std::vector<std::string> ids;
+  std::vector<const char *> id_ptr;
+};
+
+struct ckm_fasta_ids {                 // ckm_fasta_ids_read: what ckm_nucseq keeps, without the text
+  std::vector<uint64_t> seq_bytes, seq_cp;
   std::vector<uint32_t> file_first;
   std::vector<std::string> ids;
   std::vector<const char *> id_ptr;

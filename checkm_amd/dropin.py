@@ -100,3 +100,11 @@ def install():
         checkm.plot.codingDensityPlots.ProdigalGeneFeatureParser = ph.ProdigalGeneFeatureParser
         checkm.plot.tetraDistPlots.readFasta = ph.readFasta
         checkm.plot.tetraDistPlots.GenomicSignatures = ph.GenomicSignatures
+    # `checkm unbinned`: ids of the bins on the host, base counts of the kept contigs on the device, both files written by the library
+    try:
+        import checkm.unbinned
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import unbinned as ub
+        checkm.unbinned.Unbinned = ub.Unbinned

@@ -620,6 +620,49 @@ int  ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint32_t sep_l
 int  ckm_refdist_coding(const char *gff_path, const char *seq_id, const int64_t *starts, const int64_t *sizes, uint64_t nwin, int64_t *out_coding /* [nwin] */,
                         int64_t *out_total);
 
+/* ---- Unbinned: `checkm unbinned` (additions to ABI 12) -------------------------------------------------------------------------
+ * Replaces Unbinned.run (checkm/unbinned.py:33-85): the contigs of an assembly that sit in no bin and have at least minSeqLen code points,
+ * written with their length and GC.
+ * ckm_fasta_ids_read: the ids, bytes and code points of every sequence of FASTA files by the rules of ckm_nucseq_read (a repeated id keeps
+ * its place and takes the later record), a file per host thread; no sequence text is kept.  No device needed.
+ * ckm_unbinned_select, on the host: keep[s] = 1 iff the id of assembly sequence s is the id of no sequence of `bins` (a hash set, ids
+ * compared byte by byte) and its code points are >= min_len; and the totals Unbinned.run logs.  bins may be NULL (no bin files); assembly may be NULL
+ * (only the bins' two totals are filled, keep is not touched).
+ * ckm_unbinned_count, on the device (checkm_amd/csrc/unbinned_dev.h, kernels_unbinned.hip): counts[s] = A, C, G, T+U after upper-casing
+ * and the code points of every sequence with keep[s] != 0, zeros for the others.  Only the tiles of kept sequences travel, in batches of
+ * at most budget_bytes of text (0: CKM_NUCSTATS_BATCH_MB, default 1024, << 20).  tile_bytes: 0 = 4096, else a multiple of 1024 up to 1 MiB.
+ * Neither changes the result.  A keep mask of zeros (or of empty sequences only) does not touch the device.  CKM_EINVAL for a NULL
+ * argument or a bad tile_bytes, before any device call.
+ * ckm_unbinned_write: the two files of Unbinned.run straight from the batch's buffers: '>' id '\n' sequence '\n' per kept sequence, and
+ * "Sequence Id\tLength\tGC\n" with one "%s\t%d\t%.2f\n" row (id, code points, (double)(g + c) * 100 / (double)(a + c + g + t)) each.  A
+ * kept sequence with a + c + g + t == 0 ends the writing after its FASTA record and before its row: *zero_seq = its index, else -1; both
+ * files are closed either way and the call returns CKM_OK.  CKM_EINVAL when counts[s][4] of a kept sequence is not the reader's code
+ * points; CKM_EIO when a file cannot be written. */
+typedef struct ckm_fasta_ids ckm_fasta_ids;
+typedef struct {
+  const char *const *seq_ids;          /* [nseq], NUL terminated */
+  const uint64_t *seq_bytes, *seq_cp;  /* [nseq] */
+  const uint32_t *file_first;          /* [nfiles + 1] */
+  uint32_t nseq, nfiles;
+} ckm_fasta_ids_view;
+typedef struct {
+  uint64_t binned_ids, binned_bases;   /* len(binnedSeqs): distinct ids; totalBinnedBases: every bin file's own sequences */
+  uint64_t all_seqs, all_bases;
+  uint64_t unbinned_seqs, unbinned_bases;
+} ckm_unbinned_totals;
+typedef struct {
+  uint64_t kept, tiles, batches, bytes;                        /* bytes: padded text of the kept tiles, what the kernel reads */
+  double   ms_stage, ms_upload, ms_count, ms_sum, ms_download, ms_total;   /* host packing; HIP events; wall of the call */
+} ckm_unbinned_timing;
+int  ckm_fasta_ids_read(const char *const *paths, uint32_t nfiles, ckm_fasta_ids **out);
+int  ckm_fasta_ids_view_get(const ckm_fasta_ids *b, ckm_fasta_ids_view *out);
+void ckm_fasta_ids_free(ckm_fasta_ids *b);
+int  ckm_unbinned_select(const ckm_fasta_ids *bins, const ckm_nucseq *assembly, int64_t min_len, uint8_t *keep /* [nseq] */, ckm_unbinned_totals *totals);
+int  ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *assembly, const uint8_t *keep, uint32_t tile_bytes, uint64_t budget_bytes, uint64_t *counts /* [nseq][5] */,
+                        ckm_unbinned_timing *timing);
+int  ckm_unbinned_write(const ckm_nucseq *assembly, const uint8_t *keep, const uint64_t *counts /* [nseq][5] */, const char *seq_path, const char *stats_path,
+                        int64_t *zero_seq);
+
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
   int32_t msv_xJ;  float msv_sc, null_sc, bias_sc;
