@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcheckm_hip.so")
 
 ABI_VERSION = 12
+ENODEV = -4                 # CKM_ENODEV of include/checkm_hip.h: no usable HIP device
 
 
 class CkmError(RuntimeError):
@@ -179,6 +180,12 @@ class UnbinnedTiming(C.Structure):
                [(f, C.c_double) for f in ("ms_stage", "ms_upload", "ms_count", "ms_sum", "ms_download", "ms_total")]
 
 
+class AaiColumns(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("ngroups", "npairs", "nbatches", "bytes")] + \
+               [("pair_off", C.POINTER(C.c_uint64)), ("mismatches", C.POINTER(C.c_int32)), ("compared", C.POINTER(C.c_int32)), ("aai", C.POINTER(C.c_double))] + \
+               [(f, C.c_double) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -215,6 +222,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_seq_windows_layout", "ckm_seq_windows_run", "ckm_seq_windows_coding",
            "ckm_refdist_check", "ckm_refdist_run", "ckm_refdist_coding",
            "ckm_fasta_ids_read", "ckm_fasta_ids_view_get", "ckm_fasta_ids_free", "ckm_unbinned_select", "ckm_unbinned_count", "ckm_unbinned_write",
+           "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -332,6 +340,11 @@ def load():
     L.ckm_unbinned_select.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(UnbinnedTotals)]
     L.ckm_unbinned_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.POINTER(UnbinnedTiming)]
     L.ckm_unbinned_write.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_char_p, C.POINTER(C.c_int64)]
+    L.ckm_aai_check.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ckm_aai_run.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.ckm_aai_columns_get.argtypes = [C.c_void_p, C.POINTER(AaiColumns)]
+    L.ckm_aai_free.argtypes = [C.c_void_p]
+    L.ckm_aai_free.restype = None
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1313,3 +1326,41 @@ def unbinned_write(seqs, keep, counts, seq_path, stats_path):
     _chk(load().ckm_unbinned_write(seqs.h, keep.ctypes.data if seqs.nseq else None, counts.ctypes.data if seqs.nseq else None, os.fsencode(seq_path),
                                    os.fsencode(stats_path), C.byref(zero)))
     return int(zero.value)
+
+
+def _aai_args(groups):
+    """(group_row_off, row_off, text) of groups given as sequences of rows (bytes, or str of ASCII): the rows back to back."""
+    rows = [r if isinstance(r, bytes) else r.encode("ascii") for g in groups for r in g]
+    group_row_off = np.zeros(len(groups) + 1, dtype=np.uint64)
+    np.cumsum([len(g) for g in groups], out=group_row_off[1:])
+    row_off = np.zeros(len(rows) + 1, dtype=np.uint64)
+    np.cumsum([len(r) for r in rows], out=row_off[1:])
+    return group_row_off, row_off, b"".join(rows)
+
+
+def aai_check(groups):
+    """ckm_aai_check: the argument tests of aai_pairs(), without a device.  Raises CkmError as aai_pairs would."""
+    group_row_off, row_off, text = _aai_args(groups)
+    _chk(load().ckm_aai_check(len(groups), group_row_off.ctypes.data, row_off.ctypes.data, text))
+
+
+def aai_pairs(ctx, groups, budget_bytes=0):
+    """Amino-acid identity between all pairs of rows of every group (ckm_aai_run): groups is a sequence of groups, a group a sequence
+    of rows of equal length (bytes, or str of ASCII).  Returns a dict: pair_off [ngroups + 1] uint64, and per pair i < j (i major, groups
+    in order) mismatches and compared (int32) and aai (float64); npairs, nbatches, bytes and the timings in ms."""
+    group_row_off, row_off, text = _aai_args(groups)
+    h = C.c_void_p()
+    _chk(load().ckm_aai_run(ctx.h, len(groups), group_row_off.ctypes.data, row_off.ctypes.data, text, int(budget_bytes), C.byref(h)))
+    try:
+        c = AaiColumns()
+        _chk(load().ckm_aai_columns_get(h, C.byref(c)))
+        k = int(c.npairs)
+        arr = np.ctypeslib.as_array
+        out = dict(npairs=k, nbatches=int(c.nbatches), bytes=int(c.bytes), pair_off=arr(c.pair_off, shape=(len(groups) + 1,)).copy())
+        for f, dt in (("mismatches", np.int32), ("compared", np.int32), ("aai", np.float64)):
+            out[f] = arr(getattr(c, f), shape=(k,)).copy() if k else np.zeros(0, dtype=dt)
+        for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total"):
+            out[f] = getattr(c, f)
+    finally:
+        load().ckm_aai_free(h)
+    return out

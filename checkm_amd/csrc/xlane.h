@@ -87,6 +87,15 @@ __device__ __forceinline__ float wave_max(float s) {
   { float a = s, b = s; swap32(a, b); s = fmaxf(a, b); }
   return s;
 }
+__device__ __forceinline__ int wave_sum(int s) {
+  s = s + dpp_i<DPP_QUAD_XOR1>(s, s);
+  s = s + dpp_i<DPP_QUAD_XOR2>(s, s);
+  s = s + dpp_i<DPP_ROW_HALF_MIRROR>(s, s);
+  s = s + dpp_i<DPP_ROW_MIRROR>(s, s);
+  { int a = s, b = s; swap16(a, b); s = a + b; }
+  { int a = s, b = s; swap32(a, b); s = a + b; }
+  return s;
+}
 __device__ __forceinline__ int wave_max(int s) {
   s = max(s, dpp_i<DPP_QUAD_XOR1>(s, s));
   s = max(s, dpp_i<DPP_QUAD_XOR2>(s, s));

@@ -10,6 +10,8 @@ import logging
 import os
 import sys
 
+import numpy as np
+
 from checkm_amd import _lib, runtime
 from checkm_amd.common import makeSurePathExists, read_fasta
 from checkm_amd.defaultValues import DefaultValues
@@ -107,7 +109,11 @@ class HmmerAligner(object):
         masked = defaultdict(list)
         for r, path in enumerate(paths):
             text = recs[r][2].upper()
-            masked[owner[r]].append(''.join(text[i - 1] if i > 0 else '-' for i in path))
+            if text.isascii():                  # one gather: byte 0 is the gap, byte i residue i
+                cols = np.frombuffer(('-' + text).encode('ascii'), dtype=np.uint8)[np.maximum(np.asarray(path, dtype=np.intp), 0)]
+                masked[owner[r]].append(cols.tobytes().decode('ascii'))
+            else:
+                masked[owner[r]].append(''.join(text[i - 1] if i > 0 else '-' for i in path))
         for j, (path, _markerId, entries) in enumerate(jobs):
             makeSurePathExists(os.path.dirname(path))
             with open(path, 'w') as fout:

@@ -663,6 +663,37 @@ int  ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *assembly, const uint8_t 
 int  ckm_unbinned_write(const ckm_nucseq *assembly, const uint8_t *keep, const uint64_t *counts /* [nseq][5] */, const char *seq_path, const char *stats_path,
                         int64_t *zero_seq);
 
+/* ---- AminoAcidIdentity: all pairs of copies of every multi-copy marker (additions to ABI 12) -----------------------------------
+ * Replaces the pair loop of AminoAcidIdentity.run and its aai() (checkm/aminoAcidIdentity.py:65-89, :127-161).  A group is one
+ * <bin>/<marker>.masked.faa: rows group_row_off[g] .. group_row_off[g + 1] - 1, row r being bytes row_off[r] .. row_off[r + 1] - 1 of
+ * `text` (rows back to back, no padding: the library packs them at its own 16-byte stride).  group_row_off holds ngroups + 1 entries,
+ * row_off group_row_off[ngroups] + 1, text row_off[last] bytes; both tables start at 0 and never fall.  Rows are compared as bytes.
+ * For every pair i < j of a group, i major and j minor, groups in the caller's order (pair_off[g] .. pair_off[g + 1] - 1 are the pairs of
+ * group g; a group of fewer than two rows has none), the device computes (checkm_amd/csrc/aai_dev.h, kernels_aai.hip):
+ *   start = the first column where neither row holds '-', or L; end = L lowered past the trailing columns where either row holds '-',
+ *   never looking at column 0 (columns 1 .. L-1 all gapped: end = 1; L = 1: end = 1; L = 0: end = 0);
+ *   over [start, end): mismatches = columns whose bytes differ (a residue against '-' and a case difference are mismatches), compared =
+ *   columns that are not '-' in both rows; aai = 0.0 for compared == 0, else 1.0 - (double)mismatches / (double)compared in IEEE double.
+ * The packed text and the outputs go through the device in batches of at most budget_bytes (0: CKM_AAI_BATCH_MB, default 64, << 20; a
+ * batch holds at least one pair); the batches never change a result.  A call without a pair does not touch the device.
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, a table that does not start at 0 or falls, rows of unequal length in a
+ * group; CKM_ERANGE for rows of more than 4096 bytes (the model limit of DESIGN §8) or more than 2^20 rows in a group.  ckm_aai_check
+ * applies the same tests and needs no device. */
+typedef struct ckm_aai ckm_aai;
+typedef struct {
+  uint64_t        ngroups, npairs;
+  uint64_t        nbatches;                 /* batches the pairs ran in */
+  uint64_t        bytes;                    /* packed text sent, over all batches */
+  const uint64_t *pair_off;                 /* [ngroups + 1] */
+  const int32_t  *mismatches, *compared;    /* [npairs] */
+  const double   *aai;                      /* [npairs] */
+  double          ms_pack, ms_upload, ms_kernel, ms_download, ms_total;   /* host packing; HIP events per phase; wall of the call */
+} ckm_aai_columns;
+int  ckm_aai_check(uint32_t ngroups, const uint64_t *group_row_off, const uint64_t *row_off, const char *text);
+int  ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group_row_off, const uint64_t *row_off, const char *text, uint64_t budget_bytes, ckm_aai **out);
+int  ckm_aai_columns_get(const ckm_aai *r, ckm_aai_columns *out);
+void ckm_aai_free(ckm_aai *r);
+
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
   int32_t msv_xJ;  float msv_sc, null_sc, bias_sc;
