@@ -13,6 +13,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "wave_const.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define AAI_HD __host__ __device__ __forceinline__
@@ -23,9 +24,9 @@
 namespace ckm {
 namespace aai {
 
-constexpr int LANE_BYTES = 16;
-constexpr int WAVE = 64;
-constexpr int WAVE_BYTES = LANE_BYTES * WAVE;
+using ckm::LANE_BYTES;
+using ckm::WAVE;
+using ckm::WAVE_BYTES;
 constexpr uint32_t MAX_L = 4096;                  // the model limit of DESIGN section 8: a masked row has one byte per match column
 constexpr int CHUNKS = MAX_L / WAVE_BYTES;        // chunks of one row a lane holds
 constexpr uint64_t MAX_ROWS = 1u << 20;           // rows of one group: n (n - 1) / 2 and the decode's square root stay far inside 2^53

@@ -34,12 +34,7 @@ std::string inflate_block(const uint8_t *in, uint32_t n, uint8_t *out, uint32_t 
 }  // namespace
 
 uint64_t batch_budget(uint64_t asked) {
-  if (!asked) {
-    const char *e = getenv("CKM_COVERAGE_BATCH_MB");
-    const long mb = e ? atol(e) : 256;
-    asked = (uint64_t)(mb > 0 ? mb : 256) << 20;
-  }
-  return std::min<uint64_t>(asked, (uint64_t)2 << 30);
+  return std::min<uint64_t>(ckm::batch_budget(asked, "CKM_COVERAGE_BATCH_MB", 256), (uint64_t)2 << 30);
 }
 
 void Reader::refuse(const std::string &what) const { throw Error(CKM_EINVAL, path_ + ": " + what); }

@@ -24,19 +24,14 @@ struct ckm_aai {
 };
 
 extern "C" int ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group_row_off, const uint64_t *row_off, const char *text, uint64_t budget_bytes, ckm_aai **out) {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const int rc = guarded([&] {
+  CallStream cs;
+  return guarded([&] {
     if (!ctx || !out) throw Error(CKM_EINVAL, "NULL argument");
     *out = nullptr;
     std::string why;
     const int kind = aai::check_args(ngroups, group_row_off, row_off, text, why);
     if (kind != aai::ARGS_OK) throw Error(kind == aai::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL, why);
-    if (!budget_bytes) {
-      const char *e = getenv("CKM_AAI_BATCH_MB");
-      const long mb = e ? atol(e) : 64;
-      budget_bytes = (uint64_t)(mb > 0 ? mb : 64) << 20;
-    }
+    budget_bytes = batch_budget(budget_bytes, "CKM_AAI_BATCH_MB", 64);
     const auto t0 = std::chrono::steady_clock::now();
     std::unique_ptr<ckm_aai> o(new ckm_aai());
     aai::Packed P;
@@ -45,19 +40,14 @@ extern "C" int ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group
     o->ngroups = ngroups; o->npairs = P.pair_off[ngroups];
     o->mismatches.resize(o->npairs); o->compared.resize(o->npairs); o->identity.resize(o->npairs);
     if (o->npairs) {
-      HIPCHK(hipSetDevice(ctx->device));
-      HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+      cs.open(ctx->device);
       DevBuf d_groups, d_off, d_text, d_out;
       PinnedBuf h_out;
       d_groups.ensure((size_t)ngroups * sizeof(aai::Group)); d_off.ensure(((size_t)ngroups + 1) * 8);
-      float ms = 0.f;
-      HIPCHK(hipEventRecord(ev[0], st));
-      HIPCHK(hipMemcpyAsync(d_groups.p, P.groups.data(), (size_t)ngroups * sizeof(aai::Group), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_off.p, P.pair_off.data(), ((size_t)ngroups + 1) * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(ev[1], st));
-      HIPCHK(hipEventSynchronize(ev[1]));
-      HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); o->ms_upload += ms;
+      cs.timed(o->ms_upload, [&] {
+        HIPCHK(hipMemcpyAsync(d_groups.p, P.groups.data(), (size_t)ngroups * sizeof(aai::Group), hipMemcpyHostToDevice, cs.st));
+        HIPCHK(hipMemcpyAsync(d_off.p, P.pair_off.data(), ((size_t)ngroups + 1) * 8, hipMemcpyHostToDevice, cs.st));
+      });
       aai::Batch B;
       uint64_t cursor = 0;
       while (aai::next_batch(P, budget_bytes, cursor, B)) {
@@ -73,18 +63,18 @@ extern "C" int ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group
         d_text.ensure(B.text_bytes); d_out.ensure((size_t)np * aai::PAIR_BYTES); h_out.ensure((size_t)np * aai::PAIR_BYTES);
         double *da = d_out.as<double>();
         int32_t *dm = reinterpret_cast<int32_t *>(da + np), *dc = dm + np;
-        HIPCHK(hipEventRecord(ev[0], st));
-        if (B.text_bytes) HIPCHK(hipMemcpyAsync(d_text.p, P.text.data() + B.text_lo, B.text_bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(ev[1], st));
-        launch_aai_pairs(st, d_text.as<uint8_t>(), B.text_lo, d_groups.as<aai::Group>(), d_off.as<uint64_t>(), B.g_lo, B.g_hi, B.p0, np, dm, dc, da);
+        cs.mark(0);
+        if (B.text_bytes) HIPCHK(hipMemcpyAsync(d_text.p, P.text.data() + B.text_lo, B.text_bytes, hipMemcpyHostToDevice, cs.st));
+        cs.mark(1);
+        launch_aai_pairs(cs.st, d_text.as<uint8_t>(), B.text_lo, d_groups.as<aai::Group>(), d_off.as<uint64_t>(), B.g_lo, B.g_hi, B.p0, np, dm, dc, da);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[2], st));
-        HIPCHK(hipMemcpyAsync(h_out.p, d_out.p, (size_t)np * aai::PAIR_BYTES, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(ev[3], st));
-        HIPCHK(hipStreamSynchronize(st));                        // the next batch reuses the text and both output buffers
-        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); o->ms_upload += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); o->ms_kernel += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[3])); o->ms_download += ms;
+        cs.mark(2);
+        HIPCHK(hipMemcpyAsync(h_out.p, d_out.p, (size_t)np * aai::PAIR_BYTES, hipMemcpyDeviceToHost, cs.st));
+        cs.mark(3);
+        HIPCHK(hipStreamSynchronize(cs.st));                        // the next batch reuses the text and both output buffers
+        o->ms_upload += cs.ms(0, 1);
+        o->ms_kernel += cs.ms(1, 2);
+        o->ms_download += cs.ms(2, 3);
         const double *ha = h_out.as<double>();
         const int32_t *hm = reinterpret_cast<const int32_t *>(ha + np), *hc = hm + np;
         memcpy(o->identity.data() + B.p0, ha, (size_t)np * 8);
@@ -97,9 +87,6 @@ extern "C" int ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group
     o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = o.release();
   });
-  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  return rc;
 }
 
 extern "C" int ckm_aai_columns_get(const ckm_aai *r, ckm_aai_columns *c) {

@@ -82,28 +82,6 @@ extern "C" int ckm_coverage_check(const ckm_coverage_params *params) {
 
 namespace {
 
-// a phase between two events on the pass's stream; the wait is part of the design: the reader's buffer is reused by the next batch
-struct PassClock {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  void open() {
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
-  }
-  template <class F> void timed(double &acc, F &&fn) {
-    HIPCHK(hipEventRecord(ev[0], st));
-    fn();
-    HIPCHK(hipEventRecord(ev[1], st));
-    HIPCHK(hipEventSynchronize(ev[1]));
-    float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    acc += ms;
-  }
-  void close() {
-    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-    if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  }
-};
-
 const char *const kRecordWhat[] = {"", "an auxiliary field runs past the record", "tag 'NM' not present", "tag 'NM' is not an integer", "an auxiliary field of unknown type",
                                    "the read has no CIGAR, so no aligned length", "a mapped read starts before its reference (pos < 0)"};
 
@@ -112,15 +90,14 @@ const char *const kRecordWhat[] = {"", "an auxiliary field runs past the record"
 // walk ends the pass with a message that names the file, the ordinal and the read.
 template <class Timing, class Check, class Begin, class Launch, class End>
 int coverage_pass(ckm_ctx *ctx, ckm_bam *b, uint64_t budget_bytes, Timing *timing, Check &&check, Begin &&begin, Launch &&launch, End &&end) {
-  PassClock ck;
-  const int rc = guarded([&] {
+  CallStream ck;      // every phase is waited for (ck.timed): the reader's buffer is reused by the next batch
+  return guarded([&] {
     check();
     memset(timing, 0, sizeof *timing);
     const auto t0 = std::chrono::steady_clock::now();
     bam::Reader &rd = *b->reader;
     const uint64_t budget = bam::batch_budget(budget_bytes);
-    HIPCHK(hipSetDevice(ctx->device));
-    ck.open();
+    ck.open(ctx->device);
     DevBuf d_data, d_off, d_err;
     d_err.ensure(8);
     uint64_t slot = cv::NO_ERROR;
@@ -157,8 +134,6 @@ int coverage_pass(ckm_ctx *ctx, ckm_bam *b, uint64_t budget_bytes, Timing *timin
     timing->ms_read = rd.timing.ms_read; timing->ms_inflate = rd.timing.ms_inflate; timing->ms_offsets = rd.timing.ms_offsets;
     timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   });
-  ck.close();
-  return rc;
 }
 
 }  // namespace
@@ -176,14 +151,14 @@ extern "C" int ckm_coverage_run(ckm_ctx *ctx, ckm_bam *b, const ckm_coverage_par
       P = {params->min_align_per, params->max_edit_dist_per, params->min_qc, params->all_reads ? 1 : 0, (int32_t)n_ref};
       cbytes = (size_t)n_ref * cv::NSLOT * 8;
     },
-    [&](PassClock &ck) {
+    [&](CallStream &ck) {
       d_cnt.ensure(cbytes + 8);
       HIPCHK(hipMemsetAsync(d_cnt.p, 0, cbytes + 8, ck.st));
     },
     [&](hipStream_t st, const uint8_t *data, const uint32_t *offsets, uint32_t nrec, uint64_t first_ordinal, unsigned long long *err_slot) {
       launch_coverage(st, data, offsets, nrec, first_ordinal, P, d_cnt.as<unsigned long long>(), err_slot);
     },
-    [&](PassClock &ck) {
+    [&](CallStream &ck) {
       if (cbytes) ck.timed(timing->ms_download, [&] { HIPCHK(hipMemcpyAsync(out_counters, d_cnt.p, cbytes, hipMemcpyDeviceToHost, ck.st)); });
     });
 }
@@ -219,7 +194,7 @@ extern "C" int ckm_coverage_windows_run(ckm_ctx *ctx, ckm_bam *b, const ckm_cove
       P = {params->min_align_per, params->max_edit_dist_per, params->all_reads ? 1 : 0, (int32_t)n_ref, (uint32_t)params->window_size};
       cbytes = n_ref * cv::NSLOT * 8; wbytes = (size_t)first[n_ref] * 8;
     },
-    [&](PassClock &ck) {
+    [&](CallStream &ck) {
       timing->slots = (uint64_t)first[n_ref];
       d_cnt.ensure(cbytes + 8); d_len.ensure(n_ref * 8 + 8); d_first.ensure(n_ref * 8 + 8); d_direct.ensure(wbytes + 8); d_diff.ensure(wbytes + 8);
       d_sums.ensure(((size_t)first[n_ref] + cw::SCAN_BLOCK - 1) / cw::SCAN_BLOCK * 8 + 8);
@@ -233,7 +208,7 @@ extern "C" int ckm_coverage_windows_run(ckm_ctx *ctx, ckm_bam *b, const ckm_cove
       launch_covwin(st, data, offsets, nrec, first_ordinal, P, d_len.as<int64_t>(), d_first.as<int64_t>(), d_cnt.as<unsigned long long>(), d_direct.as<unsigned long long>(),
                     d_diff.as<unsigned long long>(), err_slot);
     },
-    [&](PassClock &ck) {
+    [&](CallStream &ck) {
       ck.timed(timing->ms_scan, [&] {
         launch_covwin_scan(ck.st, d_direct.as<unsigned long long>(), d_diff.as<unsigned long long>(), d_sums.as<unsigned long long>(), (uint32_t)first[n_ref]);
         HIPCHK(hipGetLastError());

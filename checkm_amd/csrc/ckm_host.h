@@ -27,8 +27,6 @@
 namespace ckm {
 
 // ---- kernel launchers (kernels_*.hip) ------------------------------------------------------------
-
-// ---- kernel launchers (kernels_*.hip) ------------------------------------------------------------
 int launch_ssv(int Q, int nblocks, int threads, hipStream_t stream, const SsvBlockWork *work, const DevModel *models,
                const uint8_t *res, const uint64_t *seq_off, const int32_t *seq_len, const uint32_t *lists, const SsvEpi &epi /* where the fused MSV finish appends */);
 void launch_msv_full(hipStream_t stream, uint32_t nblocks, WorkQueue queue, const PairRec *pairs, const DevModel *models, const LenEntry *lentab,
@@ -217,6 +215,40 @@ struct Stager {
     }
   }
   ~Stager() { for (auto &e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+// The stream and the timing events of one call of a single-stream pass.  Declared OUTSIDE the call's guarded(...): when the call fails,
+// the lambda unwinds (its DevBufs go through hipFree), guarded drains the device, and only then do the events and the stream go; on the
+// normal path the DevBufs go back to the cache behind the call's last synchronisation.  A call without device work never opens it.
+struct CallStream {
+  hipStream_t st = nullptr;
+  hipEvent_t ev[8] = {};
+  bool own = false;
+  void open(int device) {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    own = true;
+    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+  }
+  void borrow(hipStream_t s) {      // events only, over a stream that belongs to somebody else (a worker's)
+    st = s;
+    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+  }
+  void mark(int k) { HIPCHK(hipEventRecord(ev[k], st)); }
+  float ms(int a, int b) { float t = 0.f; HIPCHK(hipEventElapsedTime(&t, ev[a], ev[b])); return t; }      // both recorded and waited for by the caller
+  // a phase between two events that the host waits for: it needs the phase's result, or reuses its buffers, before the next one
+  template <class F> void timed(double &acc, F &&fn) {
+    mark(0);
+    fn();
+    mark(1);
+    HIPCHK(hipEventSynchronize(ev[1]));
+    acc += ms(0, 1);
+  }
+  ~CallStream() {
+    for (auto &e : ev) if (e) (void)hipEventDestroy(e);
+    if (own) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+  }
+  CallStream() = default; CallStream(const CallStream &) = delete; CallStream &operator=(const CallStream &) = delete;
 };
 
 }  // namespace ckm

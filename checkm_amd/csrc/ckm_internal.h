@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <cstddef>
+#include <cstdlib>
 #include <string>
 #include <vector>
 #include <stdexcept>
@@ -21,6 +22,14 @@ struct Error : std::runtime_error {
 };
 
 void set_last_error(const std::string &m);
+
+// The byte budget of a batched pass: what the caller asked for, or the variable's megabytes, or the default when it is unset or not positive
+inline uint64_t batch_budget(uint64_t asked, const char *env, long default_mb) {
+  if (asked) return asked;
+  const char *e = getenv(env);
+  const long mb = e ? strtol(e, nullptr, 10) : default_mb;
+  return (uint64_t)(mb > 0 ? mb : default_mb) << 20;
+}
 
 // One record of a HMMER3/f file, probabilities (not -ln p).
 struct HostHMM {

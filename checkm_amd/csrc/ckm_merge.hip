@@ -42,55 +42,39 @@ extern "C" int ckm_merge_check(uint32_t nbins, uint32_t ngenes, const uint64_t *
 
 extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, const uint64_t *member_bits, const int64_t *hit_sum, const int32_t *n_markers,
                              const double *thr, const char *const *bin_ids, const char *append_path, uint64_t budget_bytes, int keep_columns, ckm_merge **out) {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  FILE *fp = nullptr;
-  const int rc = guarded([&] {
+  CallStream cs;
+  std::unique_ptr<FILE, int (*)(FILE *)> fp(nullptr, fclose);      // an error leaves the file closed
+  return guarded([&] {
     if (!ctx || !out) throw Error(CKM_EINVAL, "NULL argument");
     *out = nullptr;
     if (append_path && !bin_ids) throw Error(CKM_EINVAL, "lines cannot be written without the bin ids");
     const std::string why = mg::check_args(nbins, ngenes, member_bits, hit_sum, n_markers, thr);
     if (!why.empty()) throw Error(CKM_EINVAL, why);
     const auto t0 = std::chrono::steady_clock::now();
-    if (!budget_bytes) {
-      const char *e = getenv("CKM_MERGE_BATCH_MB");
-      const long mb = e ? atol(e) : 256;
-      budget_bytes = (uint64_t)(mb > 0 ? mb : 256) << 20;
-    }
+    budget_bytes = batch_budget(budget_bytes, "CKM_MERGE_BATCH_MB", 256);
     const uint64_t cap_pairs = mg::budget_pairs(budget_bytes);
     const mg::Thresholds T = {thr[0], thr[1], thr[2], thr[3]};
     std::unique_ptr<ckm_merge> o(new ckm_merge());
     o->kept = keep_columns != 0;
     o->compared = (uint64_t)nbins * (nbins ? nbins - 1 : 0) / 2;
     if (append_path) {
-      fp = fopen(append_path, "ab");
+      fp.reset(fopen(append_path, "ab"));
       if (!fp) throw Error(CKM_EIO, std::string("cannot append to ") + append_path);
     }
     if (nbins > 1) {
       const uint32_t nwords = mg::words_for(ngenes), ntj = mg::tiles_for(nbins);
       const size_t nb = nbins;
-      HIPCHK(hipSetDevice(ctx->device));
-      HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      for (auto &e : ev) HIPCHK(hipEventCreate(&e));
-      // a phase between two events; the wait is part of the design: the host needs every phase's result before the next one
-      auto timed = [&](double &acc, auto &&fn) {
-        HIPCHK(hipEventRecord(ev[0], st));
-        fn();
-        HIPCHK(hipEventRecord(ev[1], st));
-        HIPCHK(hipEventSynchronize(ev[1]));
-        float ms = 0; HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        acc += ms;
-      };
+      cs.open(ctx->device);      // every phase below is waited for (cs.timed): the host needs its result before the next one
       DevBuf d_bits, d_sum, d_n, d_stat, d_count, d_total, d_base, d_out;
       PinnedBuf h_out;
       d_bits.ensure(nb * nwords * 8); d_sum.ensure(nb * 8); d_n.ensure(nb * 4); d_stat.ensure(nb * 16);
-      timed(o->ms_upload, [&] {
-        HIPCHK(hipMemcpyAsync(d_bits.p, member_bits, nb * nwords * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_sum.p, hit_sum, nb * 8, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_n.p, n_markers, nb * 4, hipMemcpyHostToDevice, st));
+      cs.timed(o->ms_upload, [&] {
+        HIPCHK(hipMemcpyAsync(d_bits.p, member_bits, nb * nwords * 8, hipMemcpyHostToDevice, cs.st));
+        HIPCHK(hipMemcpyAsync(d_sum.p, hit_sum, nb * 8, hipMemcpyHostToDevice, cs.st));
+        HIPCHK(hipMemcpyAsync(d_n.p, n_markers, nb * 4, hipMemcpyHostToDevice, cs.st));
       });
       const MergeBins B = {d_bits.as<uint64_t>(), d_sum.as<int64_t>(), d_n.as<int32_t>(), d_stat.as<double>(), d_stat.as<double>() + nb, nbins, nwords};
-      timed(o->ms_bins, [&] { launch_merge_bins(st, B); HIPCHK(hipGetLastError()); });
+      cs.timed(o->ms_bins, [&] { launch_merge_bins(cs.st, B); HIPCHK(hipGetLastError()); });
       const uint32_t pass_rows = mg::count_pass_rows(nbins);
       d_count.ensure((size_t)pass_rows * ntj * 4); d_total.ensure((size_t)pass_rows * 4); d_base.ensure((size_t)pass_rows * 8);
       std::vector<uint32_t> row_total(pass_rows);
@@ -100,11 +84,11 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
       for (uint32_t r0 = 0; r0 < nbins; r0 += pass_rows) {
         const uint32_t r1 = std::min<uint64_t>(nbins, (uint64_t)r0 + pass_rows), nr = r1 - r0;
         MergeOut none = {nullptr, 0, 0, nullptr, nullptr, nullptr};
-        timed(o->ms_count, [&] { launch_merge_tiles(st, false, B, T, r0, r1, r0, d_count.as<uint32_t>(), none); HIPCHK(hipGetLastError()); });
-        timed(o->ms_scan, [&] {
-          launch_merge_scan(st, r0, nr, ntj, d_count.as<uint32_t>(), d_total.as<uint32_t>());
+        cs.timed(o->ms_count, [&] { launch_merge_tiles(cs.st, false, B, T, r0, r1, r0, d_count.as<uint32_t>(), none); HIPCHK(hipGetLastError()); });
+        cs.timed(o->ms_scan, [&] {
+          launch_merge_scan(cs.st, r0, nr, ntj, d_count.as<uint32_t>(), d_total.as<uint32_t>());
           HIPCHK(hipGetLastError());
-          HIPCHK(hipMemcpyAsync(row_total.data(), d_total.p, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+          HIPCHK(hipMemcpyAsync(row_total.data(), d_total.p, (size_t)nr * 4, hipMemcpyDeviceToHost, cs.st));
         });
         const auto s0 = std::chrono::steady_clock::now();
         uint64_t run = 0;
@@ -113,7 +97,7 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
         mg::plan_groups(row_total.data(), r0, r1, cap_pairs, groups);
         o->ms_scan += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
         if (!run) continue;
-        timed(o->ms_scan, [&] { HIPCHK(hipMemcpyAsync(d_base.p, row_base.data(), (size_t)nr * 8, hipMemcpyHostToDevice, st)); });
+        cs.timed(o->ms_scan, [&] { HIPCHK(hipMemcpyAsync(d_base.p, row_base.data(), (size_t)nr * 8, hipMemcpyHostToDevice, cs.st)); });
         for (const mg::Group &g : groups) {
           const uint64_t n = g.npairs;
           d_out.ensure(n * mg::PAIR_BYTES); h_out.ensure(n * mg::PAIR_BYTES);
@@ -121,8 +105,8 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
           double *dc = d_out.as<double>();
           uint32_t *di = reinterpret_cast<uint32_t *>(dc + mg::NCOL * n);
           const MergeOut mo = {d_base.as<uint64_t>(), g.base, n, di, di + n, dc};
-          timed(o->ms_fill, [&] { launch_merge_tiles(st, true, B, T, g.row_lo, g.row_hi, r0, d_count.as<uint32_t>(), mo); HIPCHK(hipGetLastError()); });
-          timed(o->ms_download, [&] { HIPCHK(hipMemcpyAsync(h_out.p, d_out.p, n * mg::PAIR_BYTES, hipMemcpyDeviceToHost, st)); });
+          cs.timed(o->ms_fill, [&] { launch_merge_tiles(cs.st, true, B, T, g.row_lo, g.row_hi, r0, d_count.as<uint32_t>(), mo); HIPCHK(hipGetLastError()); });
+          cs.timed(o->ms_download, [&] { HIPCHK(hipMemcpyAsync(h_out.p, d_out.p, n * mg::PAIR_BYTES, hipMemcpyDeviceToHost, cs.st)); });
           const double *hc = h_out.as<double>();
           const uint32_t *hi = reinterpret_cast<const uint32_t *>(hc + mg::NCOL * n), *hj = hi + n;
           if (o->kept) {
@@ -136,7 +120,7 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
               const uint64_t m = std::min<uint64_t>(STEP, n - k);
               lines.clear();
               mg::format_lines(lines, bin_ids, hi + k, hj + k, hc + k, n, m);
-              if (fwrite(lines.data(), 1, lines.size(), fp) != lines.size()) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
+              if (fwrite(lines.data(), 1, lines.size(), fp.get()) != lines.size()) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
             }
             o->ms_write += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
           }
@@ -144,17 +128,10 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
         }
       }
     }
-    if (fp) {
-      FILE *f = fp; fp = nullptr;
-      if (fclose(f) != 0) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
-    }
+    if (fp && fclose(fp.release()) != 0) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
     o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = o.release();
   });
-  if (fp) fclose(fp);
-  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  return rc;
 }
 
 extern "C" int ckm_merge_columns_get(const ckm_merge *r, ckm_merge_columns *c) {

@@ -22,17 +22,14 @@ struct ckm_nucstats {
 };
 
 extern "C" int ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, uint32_t tile_bytes, ckm_nucstats **out) {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const int rc = guarded([&] {
+  CallStream cs;
+  return guarded([&] {
     if (!ctx || !b || !out) throw Error(CKM_EINVAL, "NULL argument");
     if (tile_bytes == 0) tile_bytes = 4096;                 // measured best of 4, 16, 64, 256 KiB (DESIGN.md section "Bin statistics")
     if (tile_bytes % ns::LANE_BYTES || tile_bytes > (1u << 20)) throw Error(CKM_EINVAL, "tile_bytes must be a multiple of 16 and at most 1 MiB");
     *out = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    cs.open(ctx->device);
     const uint32_t nseq = (uint32_t)b->seq_off.size();
     std::unique_ptr<ckm_nucstats> o(new ckm_nucstats());
     o->nseq = nseq;
@@ -45,22 +42,22 @@ extern "C" int ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, ui
     d_text.ensure(b->text.size()); d_tiles.ensure(std::max<size_t>(1, nt) * sizeof(ns::Tile)); d_canon.ensure(256);
     d_cnt.ensure(std::max<size_t>(1, nt) * ns::NCOUNT * 4);
     if (tetra) d_tetra.ensure(std::max<size_t>(1, nseq) * ns::NKMER * 4);
-    HIPCHK(hipEventRecord(ev[0], st));
-    HIPCHK(hipMemcpyAsync(d_text.p, b->text.data(), b->text.size(), hipMemcpyHostToDevice, st));
-    if (nt) HIPCHK(hipMemcpyAsync(d_tiles.p, tiles.data(), nt * sizeof(ns::Tile), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, st));
-    if (tetra) HIPCHK(hipMemsetAsync(d_tetra.p, 0, std::max<size_t>(1, nseq) * ns::NKMER * 4, st));
-    HIPCHK(hipEventRecord(ev[1], st));
-    launch_nucstats_count(st, d_text.as<uint8_t>(), d_tiles.as<ns::Tile>(), nt, d_canon.as<uint8_t>(), d_cnt.as<uint32_t>(), tetra ? d_tetra.as<uint32_t>() : nullptr);
+    cs.mark(0);
+    HIPCHK(hipMemcpyAsync(d_text.p, b->text.data(), b->text.size(), hipMemcpyHostToDevice, cs.st));
+    if (nt) HIPCHK(hipMemcpyAsync(d_tiles.p, tiles.data(), nt * sizeof(ns::Tile), hipMemcpyHostToDevice, cs.st));
+    HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, cs.st));
+    if (tetra) HIPCHK(hipMemsetAsync(d_tetra.p, 0, std::max<size_t>(1, nseq) * ns::NKMER * 4, cs.st));
+    cs.mark(1);
+    launch_nucstats_count(cs.st, d_text.as<uint8_t>(), d_tiles.as<ns::Tile>(), nt, d_canon.as<uint8_t>(), d_cnt.as<uint32_t>(), tetra ? d_tetra.as<uint32_t>() : nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[2], st));
+    cs.mark(2);
     std::vector<uint32_t> cnt((size_t)nt * ns::NCOUNT);
-    if (nt) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    if (nt) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, cnt.size() * 4, hipMemcpyDeviceToHost, cs.st));
     if (tetra) {
       o->tetra.resize((size_t)nseq * ns::NKMER);
-      if (nseq) HIPCHK(hipMemcpyAsync(o->tetra.data(), d_tetra.p, o->tetra.size() * 4, hipMemcpyDeviceToHost, st));
+      if (nseq) HIPCHK(hipMemcpyAsync(o->tetra.data(), d_tetra.p, o->tetra.size() * 4, hipMemcpyDeviceToHost, cs.st));
     }
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipStreamSynchronize(cs.st));
     std::vector<uint64_t> ev_off, nonn_base;
     ns::scan_tiles(tiles, cnt.data(), ev_off, nonn_base);
     const uint64_t nev = ev_off.empty() ? 0 : ev_off.back();
@@ -68,27 +65,22 @@ extern "C" int ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, ui
     float ms_fill = 0.f;
     if (nev) {
       d_evoff.ensure(ev_off.size() * 8); d_base.ensure(nonn_base.size() * 8); d_ev.ensure(nev * 8);
-      HIPCHK(hipMemcpyAsync(d_evoff.p, ev_off.data(), ev_off.size() * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_base.p, nonn_base.data(), nonn_base.size() * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(ev[3], st));
-      launch_nucstats_fill(st, d_text.as<uint8_t>(), d_tiles.as<ns::Tile>(), nt, d_evoff.as<uint64_t>(), d_base.as<uint64_t>(), d_ev.as<uint64_t>());
+      HIPCHK(hipMemcpyAsync(d_evoff.p, ev_off.data(), ev_off.size() * 8, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_base.p, nonn_base.data(), nonn_base.size() * 8, hipMemcpyHostToDevice, cs.st));
+      cs.mark(3);
+      launch_nucstats_fill(cs.st, d_text.as<uint8_t>(), d_tiles.as<ns::Tile>(), nt, d_evoff.as<uint64_t>(), d_base.as<uint64_t>(), d_ev.as<uint64_t>());
       HIPCHK(hipGetLastError());
-      hipEvent_t e4; HIPCHK(hipEventCreate(&e4)); HIPCHK(hipEventRecord(e4, st));
-      HIPCHK(hipMemcpyAsync(evs.data(), d_ev.p, nev * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipEventElapsedTime(&ms_fill, ev[3], e4)); (void)hipEventDestroy(e4);
+      cs.mark(4);
+      HIPCHK(hipMemcpyAsync(evs.data(), d_ev.p, nev * 8, hipMemcpyDeviceToHost, cs.st));
+      HIPCHK(hipStreamSynchronize(cs.st));
+      ms_fill = cs.ms(3, 4);
     }
     ns::assemble(tiles, cnt.data(), ev_off, evs.data(), nseq, o->count, o->piece_off, o->piece_len);
-    float a = 0.f, c = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, ev[0], ev[1])); HIPCHK(hipEventElapsedTime(&c, ev[1], ev[2]));
-    o->ms_upload = a; o->ms_count = c; o->ms_fill = ms_fill;
+    o->ms_upload = cs.ms(0, 1); o->ms_count = cs.ms(1, 2); o->ms_fill = ms_fill;
     o->bytes = b->text.size(); o->tiles = nt; o->run_starts = nev;
     o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = o.release();
   });
-  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  return rc;
 }
 
 extern "C" int ckm_nucstats_columns_get(const ckm_nucstats *r, ckm_nucstats_columns *c) {

@@ -22,6 +22,7 @@ struct ckm_orf {
 };
 
 extern "C" int ckm_orf_scan(ckm_ctx *ctx, const char *text, const uint64_t *contig_off, uint32_t ncontigs, int trans_table, int closed, ckm_orf **out) {
+  CallStream cs;      // the worker's stream, borrowed: only the events are this call's
   return guarded([&] {
     if (!ctx || !text || !contig_off || !out) throw Error(CKM_EINVAL, "NULL argument");
     if (trans_table != 11 && trans_table != 4) throw Error(CKM_EINVAL, "translation table must be 11 or 4 (checkm/prodigal.py:86-93)");
@@ -50,32 +51,28 @@ extern "C" int ckm_orf_scan(ckm_ctx *ctx, const char *text, const uint64_t *cont
       HIPCHK(hipMemcpyAsync(d_len.p, len.data(), ncontigs * 4, hipMemcpyHostToDevice, st));
     }
     HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8, st));
-    hipEvent_t e0, e1, e2;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventCreate(&e2));
+    cs.borrow(st);
     std::unique_ptr<ckm_orf> o(new ckm_orf());
     o->bases = bases; o->padded_bytes = body;
     // a bacterial genome carries about one start / stop node per 12 bases; a too-small table is detected and the chain kernel runs again
     unsigned long long cap = std::max<unsigned long long>(1 << 16, bases / 6);
     unsigned long long n = 0;
     const uint8_t *tx = d_text.as<uint8_t>() + 64; uint8_t *fl = d_flags.as<uint8_t>();
-    HIPCHK(hipEventRecord(e0, st));
+    cs.mark(0);
     launch_orf_flags(st, tx, fl, body);
-    HIPCHK(hipEventRecord(e1, st));
+    cs.mark(1);
     for (int attempt = 0; attempt < 2; ++attempt) {
       d_nodes.ensure((size_t)cap * sizeof(OrfNodeH));
-      if (attempt) { HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8, st)); HIPCHK(hipEventRecord(e1, st)); }
+      if (attempt) { HIPCHK(hipMemsetAsync(d_cnt.p, 0, 8, st)); cs.mark(1); }
       launch_orf_chain(st, fl, body / 64, d_off.as<uint64_t>(), d_len.as<int32_t>(), ncontigs, trans_table == 4 ? 1 : 0, closed ? 1 : 0, d_nodes.p, d_cnt.as<unsigned long long>(), cap);
-      HIPCHK(hipEventRecord(e2, st));
+      cs.mark(2);
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(&n, d_cnt.p, 8, hipMemcpyDeviceToHost, st));
       HIPCHK(hipStreamSynchronize(st));
       if (n <= cap) break;
       cap = n + 1024;
     }
-    float a = 0.f, b = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, e0, e1)); HIPCHK(hipEventElapsedTime(&b, e1, e2));
-    o->ms_flags = a; o->ms_chain = b;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
+    o->ms_flags = cs.ms(0, 1); o->ms_chain = cs.ms(1, 2);
     std::vector<OrfNodeH> nodes((size_t)n);
     if (n) HIPCHK(hipMemcpy(nodes.data(), d_nodes.p, (size_t)n * sizeof(OrfNodeH), hipMemcpyDeviceToHost));
     // prodigal's working order (node.c: compare_nodes -- position, then the forward strand first), made total
@@ -106,6 +103,7 @@ extern "C" void ckm_orf_free(ckm_orf *o) { delete o; }
 // measurement hook: the streaming flag kernel over `nbytes` of device-generated nucleotides (larger than the 256 MB last-level cache when
 // an HBM figure is wanted), `reps` launches timed with HIP events on the stream they run on; *ms = average duration of one launch
 extern "C" int ckm_debug_orf_flags(ckm_ctx *ctx, uint64_t nbytes, uint32_t reps, double *ms) {
+  CallStream cs;
   return guarded([&] {
     if (!ctx || !ms || !reps) throw Error(CKM_EINVAL, "bad argument");
     ctx->settle();
@@ -116,16 +114,12 @@ extern "C" int ckm_debug_orf_flags(ckm_ctx *ctx, uint64_t nbytes, uint32_t reps,
     d_text.ensure(n + 256); d_flags.ensure(n + 256);
     launch_orf_fill(st, d_text.as<uint8_t>(), n + 192, 12345u);
     launch_orf_flags(st, d_text.as<uint8_t>() + 64, d_flags.as<uint8_t>(), n);        // warm-up
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    HIPCHK(hipEventRecord(e0, st));
+    cs.borrow(st);
+    cs.mark(0);
     for (uint32_t r = 0; r < reps; ++r) launch_orf_flags(st, d_text.as<uint8_t>() + 64, d_flags.as<uint8_t>(), n);
-    HIPCHK(hipEventRecord(e1, st));
+    cs.mark(1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    *ms = (double)t / reps;
+    *ms = (double)cs.ms(0, 1) / reps;
   });
 }

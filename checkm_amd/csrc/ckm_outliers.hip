@@ -31,9 +31,8 @@ struct ckm_outliers {
 
 extern "C" int ckm_outliers_run(ckm_ctx *ctx, const ckm_nucseq *b, const uint64_t *count, const double *sig, const int64_t *coding_per_seq,
                                 const ckm_outlier_bounds *bounds, int64_t *zero_seq, ckm_outliers **out) {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  const int rc = guarded([&] {
+  CallStream cs;
+  return guarded([&] {
     if (!ctx || !b || !count || !sig || !coding_per_seq || !bounds || !zero_seq || !out) throw Error(CKM_EINVAL, "NULL argument");
     *out = nullptr; *zero_seq = -1;
     const auto t0 = std::chrono::steady_clock::now();
@@ -72,66 +71,59 @@ extern "C" int ckm_outliers_run(ckm_ctx *ctx, const ckm_nucseq *b, const uint64_
     o->seq.assign((size_t)nseq * 6, 0.0); o->flags.assign(nseq, 0);
     o->mean_gc.assign(nbins, 0.0); o->mean_cd.assign(nbins, 0.0); o->bin_sig.assign((size_t)nbins * ol::NSIG, 0.0);
     if (nseq) {
-      HIPCHK(hipSetDevice(ctx->device));
-      HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+      cs.open(ctx->device);
       DevBuf d_count, d_sig, d_coding, d_seqbin, d_first, d_order, d_sum, d_seq, d_flags, d_mean, d_binsig, d_tab, d_tabidx;
       const size_t n = nseq;
       d_count.ensure(n * 64); d_sig.ensure(n * ol::NSIG * 8); d_coding.ensure(n * 8); d_seqbin.ensure(n * 4);
       d_first.ensure(((size_t)nbins + 1) * 4); d_order.ensure((size_t)nbins * 4); d_sum.ensure((size_t)nbins * 32);
       d_seq.ensure(n * 48); d_flags.ensure(n); d_mean.ensure((size_t)nbins * 16); d_binsig.ensure((size_t)nbins * ol::NSIG * 8);
       d_tab.ensure((size_t)nrows * 24 + ((size_t)B.ntables + 1) * 4 + 8); d_tabidx.ensure((size_t)nbins * 8);
-      HIPCHK(hipEventRecord(ev[0], st));
-      HIPCHK(hipMemcpyAsync(d_count.p, count, n * 64, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_sig.p, sig, n * ol::NSIG * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_coding.p, coding_per_seq, n * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_seqbin.p, seq_bin.data(), n * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_first.p, b->file_first.data(), ((size_t)nbins + 1) * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_order.p, order.data(), (size_t)nbins * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_sum.p, bin_sum.data(), (size_t)nbins * 32, hipMemcpyHostToDevice, st));
+      cs.mark(0);
+      HIPCHK(hipMemcpyAsync(d_count.p, count, n * 64, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_sig.p, sig, n * ol::NSIG * 8, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_coding.p, coding_per_seq, n * 8, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_seqbin.p, seq_bin.data(), n * 4, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_first.p, b->file_first.data(), ((size_t)nbins + 1) * 4, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_order.p, order.data(), (size_t)nbins * 4, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_sum.p, bin_sum.data(), (size_t)nbins * 32, hipMemcpyHostToDevice, cs.st));
       // tables: key, lo, hi (nrows doubles each), then tab_off
       double *tk = d_tab.as<double>();
-      HIPCHK(hipMemcpyAsync(tk, B.key, (size_t)nrows * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(tk + nrows, B.lo, (size_t)nrows * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(tk + 2 * (size_t)nrows, B.hi, (size_t)nrows * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(tk, B.key, (size_t)nrows * 8, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(tk + nrows, B.lo, (size_t)nrows * 8, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(tk + 2 * (size_t)nrows, B.hi, (size_t)nrows * 8, hipMemcpyHostToDevice, cs.st));
       uint32_t *toff = reinterpret_cast<uint32_t *>(tk + 3 * (size_t)nrows);
-      HIPCHK(hipMemcpyAsync(toff, B.tab_off, ((size_t)B.ntables + 1) * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(hipMemcpyAsync(toff, B.tab_off, ((size_t)B.ntables + 1) * 4, hipMemcpyHostToDevice, cs.st));
       uint32_t *gct = d_tabidx.as<uint32_t>(), *cdt = gct + nbins;
-      HIPCHK(hipMemcpyAsync(gct, B.bin_gc_tab, (size_t)nbins * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(cdt, B.bin_cd_tab, (size_t)nbins * 4, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(ev[1], st));
+      HIPCHK(hipMemcpyAsync(gct, B.bin_gc_tab, (size_t)nbins * 4, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(cdt, B.bin_cd_tab, (size_t)nbins * 4, hipMemcpyHostToDevice, cs.st));
+      cs.mark(1);
       double *ds = d_seq.as<double>();
       const ol::SeqCols cols = {ds, ds + n, ds + 2 * n, ds + 3 * n, ds + 5 * n, ds + 4 * n, d_flags.as<uint8_t>()};
       double *mgc = d_mean.as<double>(), *mcd = mgc + nbins;
-      launch_outliers_seq(st, nseq, d_seqbin.as<uint32_t>(), d_first.as<uint32_t>(), d_count.as<uint64_t>(), d_coding.as<int64_t>(), d_sum.as<uint64_t>(), mgc, mcd, cols);
+      launch_outliers_seq(cs.st, nseq, d_seqbin.as<uint32_t>(), d_first.as<uint32_t>(), d_count.as<uint64_t>(), d_coding.as<int64_t>(), d_sum.as<uint64_t>(), mgc, mcd, cols);
       HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev[2], st));
-      launch_outliers_binsig(st, nbins, d_order.as<uint32_t>(), d_first.as<uint32_t>(), d_sig.as<double>(), cols.w, d_binsig.as<double>());
+      cs.mark(2);
+      launch_outliers_binsig(cs.st, nbins, d_order.as<uint32_t>(), d_first.as<uint32_t>(), d_sig.as<double>(), cols.w, d_binsig.as<double>());
       HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev[3], st));
-      launch_outliers_td(st, nseq, d_seqbin.as<uint32_t>(), d_sig.as<double>(), d_binsig.as<double>(), cols.td);
+      cs.mark(3);
+      launch_outliers_td(cs.st, nseq, d_seqbin.as<uint32_t>(), d_sig.as<double>(), d_binsig.as<double>(), cols.td);
       HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev[4], st));
+      cs.mark(4);
       const ol::Tables T = {toff, tk, tk + nrows, tk + 2 * (size_t)nrows};
-      launch_outliers_flags(st, nseq, d_seqbin.as<uint32_t>(), d_count.as<uint64_t>(), T, gct, cdt, B.td_tab, cols);
+      launch_outliers_flags(cs.st, nseq, d_seqbin.as<uint32_t>(), d_count.as<uint64_t>(), T, gct, cdt, B.td_tab, cols);
       HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev[5], st));
-      HIPCHK(hipMemcpyAsync(o->seq.data(), d_seq.p, n * 48, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(o->flags.data(), d_flags.p, n, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(o->mean_gc.data(), mgc, (size_t)nbins * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(o->mean_cd.data(), mcd, (size_t)nbins * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipMemcpyAsync(o->bin_sig.data(), d_binsig.p, (size_t)nbins * ol::NSIG * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipStreamSynchronize(st));
-      float ms[5] = {0, 0, 0, 0, 0};
-      for (int k = 0; k < 5; ++k) HIPCHK(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-      o->ms_upload = ms[0]; o->ms_seq = ms[1]; o->ms_binsig = ms[2]; o->ms_td = ms[3]; o->ms_flags = ms[4];
+      cs.mark(5);
+      HIPCHK(hipMemcpyAsync(o->seq.data(), d_seq.p, n * 48, hipMemcpyDeviceToHost, cs.st));
+      HIPCHK(hipMemcpyAsync(o->flags.data(), d_flags.p, n, hipMemcpyDeviceToHost, cs.st));
+      HIPCHK(hipMemcpyAsync(o->mean_gc.data(), mgc, (size_t)nbins * 8, hipMemcpyDeviceToHost, cs.st));
+      HIPCHK(hipMemcpyAsync(o->mean_cd.data(), mcd, (size_t)nbins * 8, hipMemcpyDeviceToHost, cs.st));
+      HIPCHK(hipMemcpyAsync(o->bin_sig.data(), d_binsig.p, (size_t)nbins * ol::NSIG * 8, hipMemcpyDeviceToHost, cs.st));
+      HIPCHK(hipStreamSynchronize(cs.st));
+      o->ms_upload = cs.ms(0, 1); o->ms_seq = cs.ms(1, 2); o->ms_binsig = cs.ms(2, 3); o->ms_td = cs.ms(3, 4); o->ms_flags = cs.ms(4, 5);
     }
     o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     *out = o.release();
   });
-  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  return rc;
 }
 
 extern "C" int ckm_outliers_columns_get(const ckm_outliers *r, ckm_outliers_columns *c) {

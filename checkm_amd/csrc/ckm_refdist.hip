@@ -21,9 +21,8 @@ using namespace ckm;
 
 extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint32_t sep_len, uint32_t block, const int64_t *starts, const int64_t *sizes, uint64_t nwin,
                                uint64_t budget_bytes, uint32_t *out_counts, double *out_td, uint64_t *out_totals, ckm_refdist_timing *timing) {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const int rc = guarded([&] {
+  CallStream cs;
+  return guarded([&] {
     if (!ctx || !b || !out_totals || !timing) throw Error(CKM_EINVAL, "NULL argument");
     const uint32_t nseq = (uint32_t)b->seq_off.size();
     const uint64_t L = rd::scaffold_len(b->seq_bytes.data(), nseq, sep_len);
@@ -34,11 +33,7 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
     for (uint32_t s = 0; s < nseq; ++s)
       if (b->seq_cp[s] != b->seq_bytes[s]) throw Error(CKM_EINVAL, "sequence " + b->ids[s] + " holds non-ASCII characters: its scaffold is not taken");
     if (block == 0) block = rd::DEFAULT_BLOCK;
-    if (budget_bytes == 0) {
-      const char *e = getenv("CKM_NUCSTATS_BATCH_MB");
-      const long mb = e ? strtol(e, nullptr, 10) : 1024;
-      budget_bytes = (uint64_t)(mb > 0 ? mb : 1024) << 20;
-    }
+    budget_bytes = batch_budget(budget_bytes, "CKM_NUCSTATS_BATCH_MB", 1024);
     const auto t0 = std::chrono::steady_clock::now();
     *timing = ckm_refdist_timing{};
     std::vector<uint8_t> text;
@@ -51,9 +46,7 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
     const uint64_t max_windows = std::max<uint64_t>(1, std::min<uint64_t>(budget_bytes / rd::TD_ROW_BYTES, rd::MAX_WINDOWS));
     const size_t scratch_rows = (size_t)std::min<uint64_t>(max_windows, std::max<uint64_t>(1, nwin));
     std::vector<uint32_t> totals(ncol, 0);
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    cs.open(ctx->device);
     uint8_t canon[256];
     ns::canonical_table(canon);
     DevBuf d_text, d_canon, d_rows, d_starts, d_sizes, d_cnt, d_tet, d_td, d_file, d_sig;
@@ -61,25 +54,24 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
     d_starts.ensure(s32.size() * 4); d_sizes.ensure(w32.size() * 4);
     if (td) { d_tet.ensure(scratch_rows * rd::TD_ROW_BYTES); d_td.ensure(s32.size() * 8); d_file.ensure(scratch_rows * 4); d_sig.ensure(ol::NSIG * 8); }
     else d_cnt.ensure(s32.size() * 8);
-    float ms = 0.f;
-    HIPCHK(hipEventRecord(ev[0], st));
-    HIPCHK(hipMemcpyAsync(d_text.p, text.data(), text.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_starts.p, s32.data(), s32.size() * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(d_sizes.p, w32.data(), w32.size() * 4, hipMemcpyHostToDevice, st));
-    if (td) HIPCHK(hipMemsetAsync(d_file.p, 0, scratch_rows * 4, st));      // every window is compared with signature 0: the genome's
-    HIPCHK(hipEventRecord(ev[1], st));
-    launch_refdist_blocks(st, d_text.as<uint8_t>(), L, block, nblocks, td ? 1 : 0, d_canon.as<uint8_t>(), d_rows.as<uint32_t>());
+    cs.mark(0);
+    HIPCHK(hipMemcpyAsync(d_text.p, text.data(), text.size(), hipMemcpyHostToDevice, cs.st));
+    HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, cs.st));
+    HIPCHK(hipMemcpyAsync(d_starts.p, s32.data(), s32.size() * 4, hipMemcpyHostToDevice, cs.st));
+    HIPCHK(hipMemcpyAsync(d_sizes.p, w32.data(), w32.size() * 4, hipMemcpyHostToDevice, cs.st));
+    if (td) HIPCHK(hipMemsetAsync(d_file.p, 0, scratch_rows * 4, cs.st));      // every window is compared with signature 0: the genome's
+    cs.mark(1);
+    launch_refdist_blocks(cs.st, d_text.as<uint8_t>(), L, block, nblocks, td ? 1 : 0, d_canon.as<uint8_t>(), d_rows.as<uint32_t>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[2], st));
-    launch_refdist_scan(st, d_rows.as<uint32_t>(), nblocks, ncol);
+    cs.mark(2);
+    launch_refdist_scan(cs.st, d_rows.as<uint32_t>(), nblocks, ncol);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(ev[3], st));
-    HIPCHK(hipMemcpyAsync(totals.data(), d_rows.as<uint8_t>() + (size_t)nblocks * row_bytes, row_bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_upload += ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); timing->ms_blocks += ms;
-    HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[3])); timing->ms_scan += ms;
+    cs.mark(3);
+    HIPCHK(hipMemcpyAsync(totals.data(), d_rows.as<uint8_t>() + (size_t)nblocks * row_bytes, row_bytes, hipMemcpyDeviceToHost, cs.st));
+    HIPCHK(hipStreamSynchronize(cs.st));
+    timing->ms_upload += cs.ms(0, 1);
+    timing->ms_blocks += cs.ms(1, 2);
+    timing->ms_scan += cs.ms(2, 3);
     for (int k = 0; k < rd::NTOTALS; ++k) out_totals[k] = 0;
     if (td) {
       // genomeSig = seqSignature(scaffold): every count over their sum, one division each
@@ -87,37 +79,34 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
       for (int k = 0; k < rd::NKMER; ++k) { out_totals[2 + k] = totals[k]; sum += totals[k]; }
       double sig[ol::NSIG];
       for (int k = 0; k < ol::NSIG; ++k) sig[k] = ol::ratio((uint64_t)totals[k], sum);
-      HIPCHK(hipMemcpyAsync(d_sig.p, sig, sizeof(sig), hipMemcpyHostToDevice, st));
-      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpyAsync(d_sig.p, sig, sizeof(sig), hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipStreamSynchronize(cs.st));
     } else {
       out_totals[0] = totals[0]; out_totals[1] = totals[1];
     }
     const uint64_t per_launch = td ? max_windows : rd::MAX_WINDOWS;   // two counters per window need no scratch: one launch takes them all
     for (uint64_t win0 = 0; win0 < nwin; win0 += per_launch) {
       const uint32_t n = (uint32_t)std::min<uint64_t>(per_launch, nwin - win0);
-      HIPCHK(hipEventRecord(ev[0], st));
-      launch_refdist_windows(st, d_text.as<uint8_t>(), block, stat, d_starts.as<uint32_t>(), d_sizes.as<uint32_t>(), win0, n, d_canon.as<uint8_t>(),
+      cs.mark(0);
+      launch_refdist_windows(cs.st, d_text.as<uint8_t>(), block, stat, d_starts.as<uint32_t>(), d_sizes.as<uint32_t>(), win0, n, d_canon.as<uint8_t>(),
                              d_rows.as<uint32_t>(), td ? nullptr : d_cnt.as<uint32_t>(), td ? d_tet.as<uint32_t>() : nullptr);
       HIPCHK(hipGetLastError());
       if (td) {
-        launch_seqwin_td(st, n, d_tet.as<uint32_t>(), d_file.as<uint32_t>(), d_sig.as<double>(), d_td.as<double>() + win0);
+        launch_seqwin_td(cs.st, n, d_tet.as<uint32_t>(), d_file.as<uint32_t>(), d_sig.as<double>(), d_td.as<double>() + win0);
         HIPCHK(hipGetLastError());
       }
-      HIPCHK(hipEventRecord(ev[1], st));
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_windows += ms;
+      cs.mark(1);
+      HIPCHK(hipStreamSynchronize(cs.st));
+      timing->ms_windows += cs.ms(0, 1);
       timing->batches += 1;
     }
-    HIPCHK(hipEventRecord(ev[0], st));
-    if (nwin && td) HIPCHK(hipMemcpyAsync(out_td, d_td.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, st));
-    if (nwin && !td) HIPCHK(hipMemcpyAsync(out_counts, d_cnt.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipEventRecord(ev[1], st));
-    HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_download += ms;
+    cs.mark(0);
+    if (nwin && td) HIPCHK(hipMemcpyAsync(out_td, d_td.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, cs.st));
+    if (nwin && !td) HIPCHK(hipMemcpyAsync(out_counts, d_cnt.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, cs.st));
+    cs.mark(1);
+    HIPCHK(hipStreamSynchronize(cs.st));
+    timing->ms_download += cs.ms(0, 1);
     timing->windows = nwin; timing->blocks = nblocks; timing->bytes = L;
     timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   });
-  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  return rc;
 }

@@ -18,20 +18,15 @@ using namespace ckm;
 extern "C" int ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t window_size, int tetra, const double *bin_sig, uint32_t piece_bytes,
                                    uint64_t budget_bytes, uint32_t *out_base_counts, uint64_t *out_seq_counts, double *out_td, uint32_t *out_tetra_counts,
                                    uint8_t *out_skipped, ckm_seq_windows_timing *timing) {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const int rc = guarded([&] {
+  CallStream cs;
+  return guarded([&] {
     if (!ctx || !b || !out_base_counts || !out_seq_counts || !out_skipped || !timing) throw Error(CKM_EINVAL, "NULL argument");
     if (window_size < 1 || (uint64_t)window_size > sw::MAX_WINDOWS) throw Error(CKM_EINVAL, "window_size must be between 1 and 2^31 - 1");
     if (!tetra && (bin_sig || out_td || out_tetra_counts)) throw Error(CKM_EINVAL, "bin_sig, out_td and out_tetra_counts need tetra != 0");
     if (tetra && ((bin_sig == nullptr) != (out_td == nullptr) || (!out_td && !out_tetra_counts))) throw Error(CKM_EINVAL, "tetra != 0 needs bin_sig with out_td, or out_tetra_counts");
     if (piece_bytes == 0) piece_bytes = sw::DEFAULT_PIECE;
     if (piece_bytes < sw::MIN_PIECE || piece_bytes > (1u << 20)) throw Error(CKM_EINVAL, "piece_bytes must be between 16 and 1 MiB");
-    if (budget_bytes == 0) {
-      const char *e = getenv("CKM_NUCSTATS_BATCH_MB");
-      const long mb = e ? strtol(e, nullptr, 10) : 1024;
-      budget_bytes = (uint64_t)(mb > 0 ? mb : 1024) << 20;
-    }
+    budget_bytes = batch_budget(budget_bytes, "CKM_NUCSTATS_BATCH_MB", 1024);
     const auto t0 = std::chrono::steady_clock::now();
     *timing = ckm_seq_windows_timing{};
     const uint32_t nseq = (uint32_t)b->seq_off.size(), nfiles = (uint32_t)b->file_first.size() - 1;
@@ -56,9 +51,7 @@ extern "C" int ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t wi
     const uint64_t max_windows = std::max<uint64_t>(1, std::min<uint64_t>(budget_bytes / sw::ROW_BYTES, sw::MAX_WINDOWS));
     std::vector<uint32_t> cnt((size_t)nrows * 4, 0);
     if (nseq) {
-      HIPCHK(hipSetDevice(ctx->device));
-      HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+      cs.open(ctx->device);
       uint8_t canon[256];
       ns::canonical_table(canon);
       const size_t scratch_rows = (size_t)std::min<uint64_t>(max_windows, std::max<uint64_t>(1, nwin));
@@ -66,55 +59,51 @@ extern "C" int ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t wi
       d_text.ensure(b->text.size()); d_canon.ensure(256); d_cnt.ensure((size_t)nrows * 16);
       if (tetra) d_tet.ensure(scratch_rows * sw::ROW_BYTES);
       if (out_td) { d_td.ensure(std::max<size_t>(1, nwin) * 8); d_binsig.ensure(std::max<size_t>(1, nfiles) * ol::NSIG * 8); }
-      float ms = 0.f;
-      HIPCHK(hipEventRecord(ev[0], st));
-      HIPCHK(hipMemcpyAsync(d_text.p, b->text.data(), b->text.size(), hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, st));
-      HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nrows * 16, st));
-      if (out_td && nfiles) HIPCHK(hipMemcpyAsync(d_binsig.p, bin_sig, (size_t)nfiles * ol::NSIG * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(ev[1], st));
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_upload += ms;
+      cs.mark(0);
+      HIPCHK(hipMemcpyAsync(d_text.p, b->text.data(), b->text.size(), hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, cs.st));
+      HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nrows * 16, cs.st));
+      if (out_td && nfiles) HIPCHK(hipMemcpyAsync(d_binsig.p, bin_sig, (size_t)nfiles * ol::NSIG * 8, hipMemcpyHostToDevice, cs.st));
+      cs.mark(1);
+      HIPCHK(hipStreamSynchronize(cs.st));
+      timing->ms_upload += cs.ms(0, 1);
       sw::Cursor cur;
       sw::Batch B;
       while (sw::next_batch(b->seq_off.data(), len.data(), out_skipped, seq_file.data(), nseq, w, piece_bytes, max_windows, nwin, cur, B)) {
         if (B.pieces.size() > 0x7FFFFFF0ull) throw Error(CKM_ERANGE, "too many pieces in one batch: use a larger piece_bytes");
         const uint32_t np = (uint32_t)B.pieces.size();
         d_pieces.ensure(std::max<size_t>(1, np) * sizeof(sw::Piece)); d_file.ensure(std::max<size_t>(1, B.nwin) * 4);
-        HIPCHK(hipEventRecord(ev[0], st));
-        if (np) HIPCHK(hipMemcpyAsync(d_pieces.p, B.pieces.data(), (size_t)np * sizeof(sw::Piece), hipMemcpyHostToDevice, st));
-        if (out_td && B.nwin) HIPCHK(hipMemcpyAsync(d_file.p, B.win_file.data(), (size_t)B.nwin * 4, hipMemcpyHostToDevice, st));
-        if (tetra && B.nwin) HIPCHK(hipMemsetAsync(d_tet.p, 0, (size_t)B.nwin * sw::ROW_BYTES, st));
-        HIPCHK(hipEventRecord(ev[1], st));
-        launch_seqwin_count(st, d_text.as<uint8_t>(), d_pieces.as<sw::Piece>(), np, d_canon.as<uint8_t>(), d_cnt.as<uint32_t>(), tetra ? d_tet.as<uint32_t>() : nullptr);
+        cs.mark(0);
+        if (np) HIPCHK(hipMemcpyAsync(d_pieces.p, B.pieces.data(), (size_t)np * sizeof(sw::Piece), hipMemcpyHostToDevice, cs.st));
+        if (out_td && B.nwin) HIPCHK(hipMemcpyAsync(d_file.p, B.win_file.data(), (size_t)B.nwin * 4, hipMemcpyHostToDevice, cs.st));
+        if (tetra && B.nwin) HIPCHK(hipMemsetAsync(d_tet.p, 0, (size_t)B.nwin * sw::ROW_BYTES, cs.st));
+        cs.mark(1);
+        launch_seqwin_count(cs.st, d_text.as<uint8_t>(), d_pieces.as<sw::Piece>(), np, d_canon.as<uint8_t>(), d_cnt.as<uint32_t>(), tetra ? d_tet.as<uint32_t>() : nullptr);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[2], st));
+        cs.mark(2);
         if (out_td) {
-          launch_seqwin_td(st, B.nwin, d_tet.as<uint32_t>(), d_file.as<uint32_t>(), d_binsig.as<double>(), d_td.as<double>() + B.win0);
+          launch_seqwin_td(cs.st, B.nwin, d_tet.as<uint32_t>(), d_file.as<uint32_t>(), d_binsig.as<double>(), d_td.as<double>() + B.win0);
           HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipEventRecord(ev[3], st));
+        cs.mark(3);
         if (out_tetra_counts && B.nwin)
-          HIPCHK(hipMemcpyAsync(out_tetra_counts + B.win0 * sw::NKMER, d_tet.p, (size_t)B.nwin * sw::ROW_BYTES, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_upload += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); timing->ms_count += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ev[2], ev[3])); timing->ms_td += ms;
+          HIPCHK(hipMemcpyAsync(out_tetra_counts + B.win0 * sw::NKMER, d_tet.p, (size_t)B.nwin * sw::ROW_BYTES, hipMemcpyDeviceToHost, cs.st));
+        HIPCHK(hipStreamSynchronize(cs.st));
+        timing->ms_upload += cs.ms(0, 1);
+        timing->ms_count += cs.ms(1, 2);
+        timing->ms_td += cs.ms(2, 3);
         timing->pieces += np; timing->batches += 1;
       }
-      HIPCHK(hipEventRecord(ev[0], st));
-      if (nrows) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, (size_t)nrows * 16, hipMemcpyDeviceToHost, st));
-      if (out_td && nwin) HIPCHK(hipMemcpyAsync(out_td, d_td.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipEventRecord(ev[1], st));
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_download += ms;
+      cs.mark(0);
+      if (nrows) HIPCHK(hipMemcpyAsync(cnt.data(), d_cnt.p, (size_t)nrows * 16, hipMemcpyDeviceToHost, cs.st));
+      if (out_td && nwin) HIPCHK(hipMemcpyAsync(out_td, d_td.p, (size_t)nwin * 8, hipMemcpyDeviceToHost, cs.st));
+      cs.mark(1);
+      HIPCHK(hipStreamSynchronize(cs.st));
+      timing->ms_download += cs.ms(0, 1);
     }
     if (nwin) memcpy(out_base_counts, cnt.data(), (size_t)nwin * 16);
     sw::seq_counts(cnt.data(), first.data(), nseq, out_seq_counts);
     timing->windows = nwin; timing->bytes = b->text.size(); timing->skipped_seqs = skipped;
     timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   });
-  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  return rc;
 }

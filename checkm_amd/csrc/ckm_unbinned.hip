@@ -17,17 +17,12 @@ using namespace ckm;
 
 extern "C" int ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *b, const uint8_t *keep, uint32_t tile_bytes, uint64_t budget_bytes, uint64_t *counts,
                                   ckm_unbinned_timing *timing) {
-  hipStream_t st = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  const int rc = guarded([&] {
+  CallStream cs;
+  return guarded([&] {
     if (!ctx || !b || !keep || !counts || !timing) throw Error(CKM_EINVAL, "NULL argument");
     if (tile_bytes == 0) tile_bytes = ub::DEFAULT_TILE;
     if (tile_bytes % ub::WAVE_BYTES || tile_bytes > ub::MAX_TILE) throw Error(CKM_EINVAL, "tile_bytes must be a multiple of 1024 and at most 1 MiB");
-    if (budget_bytes == 0) {
-      const char *e = getenv("CKM_NUCSTATS_BATCH_MB");
-      const long mb = e ? strtol(e, nullptr, 10) : 1024;
-      budget_bytes = (uint64_t)(mb > 0 ? mb : 1024) << 20;
-    }
+    budget_bytes = batch_budget(budget_bytes, "CKM_NUCSTATS_BATCH_MB", 1024);
     const auto t0 = std::chrono::steady_clock::now();
     *timing = ckm_unbinned_timing{};
     const uint32_t nseq = (uint32_t)b->seq_off.size();
@@ -39,15 +34,12 @@ extern "C" int ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *b, const uint8
     const uint32_t nkept = (uint32_t)kept.size();
     timing->kept = nkept; timing->tiles = tiles.size();
     if (!tiles.empty()) {
-      HIPCHK(hipSetDevice(ctx->device));
-      HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+      cs.open(ctx->device);
       DevBuf d_text, d_tiles, d_rows, d_first, d_out;
       d_rows.ensure(tiles.size() * ub::NCOUNT * 4);
       std::vector<char> stage;
       ub::Batch B;
       uint64_t cursor = 0;
-      float ms = 0.f;
       while (ub::next_batch(tiles, budget_bytes, cursor, B)) {
         if (B.tiles.size() > 0x7FFFFFF0ull) throw Error(CKM_ERANGE, "too many tiles in one batch: use a larger tile_bytes or a smaller budget");
         const uint32_t nt = (uint32_t)B.tiles.size();
@@ -63,35 +55,32 @@ extern "C" int ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *b, const uint8
         }
         timing->ms_stage += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
         d_text.ensure(B.bytes); d_tiles.ensure((size_t)nt * sizeof(ub::Tile));
-        HIPCHK(hipEventRecord(ev[0], st));
-        HIPCHK(hipMemcpyAsync(d_text.p, src, B.bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d_tiles.p, B.tiles.data(), (size_t)nt * sizeof(ub::Tile), hipMemcpyHostToDevice, st));
-        HIPCHK(hipEventRecord(ev[1], st));
-        launch_unbinned_count(st, d_text.as<uint8_t>(), d_tiles.as<ub::Tile>(), nt, d_rows.as<uint32_t>() + B.t0 * ub::NCOUNT);
+        cs.mark(0);
+        HIPCHK(hipMemcpyAsync(d_text.p, src, B.bytes, hipMemcpyHostToDevice, cs.st));
+        HIPCHK(hipMemcpyAsync(d_tiles.p, B.tiles.data(), (size_t)nt * sizeof(ub::Tile), hipMemcpyHostToDevice, cs.st));
+        cs.mark(1);
+        launch_unbinned_count(cs.st, d_text.as<uint8_t>(), d_tiles.as<ub::Tile>(), nt, d_rows.as<uint32_t>() + B.t0 * ub::NCOUNT);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(ev[2], st));
-        HIPCHK(hipStreamSynchronize(st));                        // the next batch reuses the text, the tiles and the staging buffer
-        HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_upload += ms;
-        HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); timing->ms_count += ms;
+        cs.mark(2);
+        HIPCHK(hipStreamSynchronize(cs.st));                        // the next batch reuses the text, the tiles and the staging buffer
+        timing->ms_upload += cs.ms(0, 1);
+        timing->ms_count += cs.ms(1, 2);
         timing->batches += 1; timing->bytes += B.bytes;
       }
       d_first.ensure(first_tile.size() * 8); d_out.ensure((size_t)nkept * ub::NCOUNT * 8);
       std::vector<uint64_t> out((size_t)nkept * ub::NCOUNT);
-      HIPCHK(hipMemcpyAsync(d_first.p, first_tile.data(), first_tile.size() * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(hipEventRecord(ev[0], st));
-      launch_unbinned_sum(st, d_rows.as<uint32_t>(), d_first.as<uint64_t>(), nkept, d_out.as<uint64_t>());
+      HIPCHK(hipMemcpyAsync(d_first.p, first_tile.data(), first_tile.size() * 8, hipMemcpyHostToDevice, cs.st));
+      cs.mark(0);
+      launch_unbinned_sum(cs.st, d_rows.as<uint32_t>(), d_first.as<uint64_t>(), nkept, d_out.as<uint64_t>());
       HIPCHK(hipGetLastError());
-      HIPCHK(hipEventRecord(ev[1], st));
-      HIPCHK(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, st));
-      HIPCHK(hipEventRecord(ev[2], st));
-      HIPCHK(hipStreamSynchronize(st));
-      HIPCHK(hipEventElapsedTime(&ms, ev[0], ev[1])); timing->ms_sum = ms;
-      HIPCHK(hipEventElapsedTime(&ms, ev[1], ev[2])); timing->ms_download = ms;
+      cs.mark(1);
+      HIPCHK(hipMemcpyAsync(out.data(), d_out.p, out.size() * 8, hipMemcpyDeviceToHost, cs.st));
+      cs.mark(2);
+      HIPCHK(hipStreamSynchronize(cs.st));
+      timing->ms_sum = cs.ms(0, 1);
+      timing->ms_download = cs.ms(1, 2);
       for (uint32_t k = 0; k < nkept; ++k) memcpy(counts + (size_t)kept[k] * ub::NCOUNT, &out[(size_t)k * ub::NCOUNT], ub::NCOUNT * 8);
     }
     timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   });
-  for (auto &e : ev) if (e) (void)hipEventDestroy(e);
-  if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-  return rc;
 }

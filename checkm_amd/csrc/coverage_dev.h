@@ -15,6 +15,7 @@
 // walk from the end stops before the first operation), or the sum of the M, I, = and X lengths when l_seq == 0.
 #pragma once
 #include <cstdint>
+#include "wave_const.h"
 
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -26,7 +27,7 @@
 namespace ckm {
 namespace cv {
 
-constexpr int WAVE = 64;
+using ckm::WAVE;
 constexpr int NCLASS = 8;
 constexpr int NSLOT = 9;                 // per reference: reads, classes 1..7, numerator
 constexpr int SLOT_READS = 0, SLOT_NUMER = 8;

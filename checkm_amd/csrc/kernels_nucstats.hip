@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "nucstats_dev.h"
+#include "tetra_wave.h"
 
 namespace ckm {
 using namespace ns;
@@ -42,12 +43,6 @@ __device__ __forceinline__ void load_lane(const uint8_t *text, const Tile &T, ui
   for (int k = 0; k < 28; ++k) b[1 + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s);
-  return x;
-}
-
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int lane) {
 #pragma unroll
   for (int s = 1; s < WAVE; s <<= 1) {
@@ -63,8 +58,7 @@ __global__ __launch_bounds__(256) void nucstats_count_kernel(const uint8_t *__re
   __shared__ uint8_t lcanon[256];
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
   const uint32_t t = blockIdx.x * 4 + wv;
-  lcanon[threadIdx.x] = canon[threadIdx.x];
-  for (int k = lane; k < NKMER; k += WAVE) hist[wv][k] = 0;
+  hist_stage(canon, lcanon, hist[wv], lane);
   __syncthreads();
   const bool active = t < ntiles;
   Tile T = {};
@@ -80,14 +74,7 @@ __global__ __launch_bounds__(256) void nucstats_count_kernel(const uint8_t *__re
 #pragma unroll
     for (int k = 0; k < 8; ++k) acc[k] += o.cnt[k];
     nev += (uint32_t)__builtin_popcount(o.ev_mask);
-    if (tetra) {
-      uint32_t m = o.kmer_mask;
-      while (m) {
-        const int j = __builtin_ctz(m);
-        m &= m - 1;
-        atomicAdd(&hist[wv][lcanon[o.code[j]]], 1u);
-      }
-    }
+    if (tetra) hist_count(o.kmer_mask, o.code, lcanon, hist[wv]);
   }
   __syncthreads();
   if (!active) return;
@@ -101,10 +88,7 @@ __global__ __launch_bounds__(256) void nucstats_count_kernel(const uint8_t *__re
   }
   if (tetra) {
     uint32_t *row = tetra + (uint64_t)T.seq * NKMER;
-    for (int k = lane; k < NKMER; k += WAVE) {
-      const uint32_t v = hist[wv][k];
-      if (v) atomicAdd(row + k, v);
-    }
+    hist_flush(lane, [=](int k) { const uint32_t v = hist[wv][k]; if (v) atomicAdd(row + k, v); });
   }
 }
 

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "refdist_dev.h"
-#include "seqwin_wave.h"
+#include "tetra_wave.h"
 
 namespace ckm {
 using namespace sw;
@@ -27,10 +27,7 @@ __global__ __launch_bounds__(256) void refdist_block_kernel(const uint8_t *__res
   __shared__ uint8_t lcanon[256];
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
   const uint32_t b = blockIdx.x * 4 + wv;
-  if (td) {                                                 // GC / CD count no 4-mers: nothing to stage
-    lcanon[threadIdx.x] = canon[threadIdx.x];
-    for (int k = lane; k < NKMER; k += WAVE) hist[wv][k] = 0;
-  }
+  if (td) hist_stage(canon, lcanon, hist[wv], lane);        // GC / CD count no 4-mers: nothing to stage
   __syncthreads();
   const bool active = b < nblocks;
   uint32_t acc[4] = {0, 0, 0, 0};
@@ -39,7 +36,7 @@ __global__ __launch_bounds__(256) void refdist_block_kernel(const uint8_t *__res
   if (!active) return;
   if (td) {
     uint32_t *row = rows + (uint64_t)b * NKMER;
-    for (int k = lane; k < NKMER; k += WAVE) row[k] = hist[wv][k];
+    hist_flush(lane, [=](int k) { row[k] = hist[wv][k]; });
   } else {
     const uint32_t gc = wave_sum(acc[1] + acc[2]), at = wave_sum(acc[0] + acc[3]);
     if (lane == 0) { rows[(uint64_t)b * 2] = gc; rows[(uint64_t)b * 2 + 1] = at; }
@@ -75,10 +72,7 @@ __global__ __launch_bounds__(256) void refdist_window_kernel(const uint8_t *__re
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
   const uint32_t x = blockIdx.x * 4 + wv;
   const bool active = x < nwin, td = stat == rd::STAT_TD;
-  if (td) {
-    lcanon[threadIdx.x] = canon[threadIdx.x];
-    for (int k = lane; k < NKMER; k += WAVE) hist[wv][k] = 0;
-  }
+  if (td) hist_stage(canon, lcanon, hist[wv], lane);
   __syncthreads();
   uint32_t acc[4] = {0, 0, 0, 0};
   rd::WindowGeom g = {};
@@ -92,7 +86,7 @@ __global__ __launch_bounds__(256) void refdist_window_kernel(const uint8_t *__re
   if (td) {
     const uint32_t *p0 = rows + g.b0 * NKMER, *p1 = rows + g.b1 * NKMER;
     uint32_t *row = tet + (uint64_t)x * NKMER;
-    for (int k = lane; k < NKMER; k += WAVE) row[k] = hist[wv][k] + (g.whole ? p1[k] - p0[k] : 0u);
+    hist_flush(lane, [=](int k) { row[k] = hist[wv][k] + (g.whole ? p1[k] - p0[k] : 0u); });
   } else {
     uint32_t gc = wave_sum(acc[1] + acc[2]), at = wave_sum(acc[0] + acc[3]);
     if (lane == 0) {

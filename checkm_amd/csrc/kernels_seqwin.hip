@@ -3,7 +3,7 @@
 // logic is sw::lane_step (seqwin_dev.h), shared with the host executor of the CPU tests; the distance is ol::td_running / ol::td_combine
 // (outlier_dev.h), the summation of outliers_td_kernel.
 //
-//   seqwin_count_kernel  a wavefront per piece (four per block), the loop sw::wave_piece (seqwin_wave.h, shared with kernels_refdist.hip).
+//   seqwin_count_kernel  a wavefront per piece (four per block), the loop sw::wave_piece (tetra_wave.h, shared with kernels_refdist.hip).
 //                        A window starts at any byte, so the wave walks 16-byte-ALIGNED spans
 //                        of 1 KiB from the chunk that holds its piece's first byte: every lane loads one aligned 128-bit word (1 KiB per
 //                        instruction, consecutive lanes at consecutive 16-byte chunks) and
@@ -18,7 +18,7 @@
 #include <cstdint>
 #include "outlier_dev.h"
 #include "seqwin_dev.h"
-#include "seqwin_wave.h"
+#include "tetra_wave.h"
 
 namespace ckm {
 using namespace sw;
@@ -29,8 +29,7 @@ __global__ __launch_bounds__(256) void seqwin_count_kernel(const uint8_t *__rest
   __shared__ uint8_t lcanon[256];
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
   const uint32_t t = blockIdx.x * 4 + wv;
-  lcanon[threadIdx.x] = canon[threadIdx.x];
-  for (int k = lane; k < NKMER; k += WAVE) hist[wv][k] = 0;
+  hist_stage(canon, lcanon, hist[wv], lane);
   __syncthreads();
   const bool active = t < npieces;
   Piece P = {};
@@ -53,11 +52,11 @@ __global__ __launch_bounds__(256) void seqwin_count_kernel(const uint8_t *__rest
   }
   if (kmers) {
     uint32_t *row = tet + (uint64_t)P.tet_row * NKMER;
-    for (int k = lane; k < NKMER; k += WAVE) {
+    hist_flush(lane, [=](int k) {
       const uint32_t v = hist[wv][k];
       if (alone) row[k] = v;
       else if (v) atomicAdd(row + k, v);
-    }
+    });
   }
 }
 

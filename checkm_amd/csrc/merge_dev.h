@@ -15,6 +15,7 @@
 // 2^46), the division second.  The library and the host executor are built with -ffp-contract=off and without fast-math.
 #pragma once
 #include <cstdint>
+#include "wave_const.h"
 
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -26,7 +27,7 @@
 namespace ckm {
 namespace mg {
 
-constexpr int WAVE = 64;
+using ckm::WAVE;
 constexpr int TILE_I = 64;                       // rows of a tile (bin I)
 constexpr int TILE_J = WAVE;                     // columns of a tile (bin J): a lane per column
 constexpr int WAVES = 4;                         // wavefronts of a block

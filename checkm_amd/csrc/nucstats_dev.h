@@ -13,6 +13,7 @@
 #pragma once
 #include <cstdint>
 #include <vector>
+#include "wave_const.h"
 
 #if defined(__HIPCC__)
 #define NS_HD __host__ __device__ __forceinline__
@@ -23,11 +24,11 @@
 namespace ckm {
 namespace ns {
 
-constexpr int LANE_BYTES = 16;
-constexpr int WAVE = 64;
-constexpr int WAVE_BYTES = LANE_BYTES * WAVE;   // one step of a wave over its tile
+using ckm::LANE_BYTES;
+using ckm::WAVE;
+using ckm::WAVE_BYTES;                           // one step of a wave over its tile
+using ckm::NKMER;
 constexpr int HALO = 12;                         // bytes after the chunk a lane looks at: 9 for a run of ten 'N', 3 for a 4-mer
-constexpr int NKMER = 136;                       // canonical tetranucleotides
 constexpr int NCOUNT = 9;                        // per-tile counters, in this order:
 enum { C_A = 0, C_C, C_G, C_TU, C_NU, C_NL, C_CP, C_NONN, C_EV };
 

@@ -15,6 +15,7 @@
 //   (d) flags          nearest sequence-length key (first minimum of |key - len| in float64) and three comparisons, false on nan
 #pragma once
 #include <cstdint>
+#include "wave_const.h"
 
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>
@@ -26,10 +27,10 @@
 namespace ckm {
 namespace ol {
 
-constexpr int NSIG = 136;          // canonical tetranucleotides: one row of the profile
+constexpr int NSIG = ckm::NKMER;   // canonical tetranucleotides: one row of the profile
 constexpr int TD_SPLIT = 64;       // numpy's pairwise sum cuts 136 elements at 64 (n / 2 rounded down to a multiple of 8)
 constexpr int TD_ACC = 8;          // running sums of one half
-constexpr int WAVE = 64;
+using ckm::WAVE;
 constexpr int TD_SEQS = WAVE / TD_ACC;   // sequences a wavefront takes at once: eight lanes (= eight running sums) each
 enum { F_GC = 1, F_CD = 2, F_TD = 4 };
 

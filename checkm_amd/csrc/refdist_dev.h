@@ -23,7 +23,7 @@ constexpr uint32_t MIN_BLOCK = 16, DEFAULT_BLOCK = 256, MAX_BLOCK = 1u << 20;
 constexpr uint32_t MAX_SEP = 1024;
 constexpr uint64_t MAX_SCAFFOLD = 0x7FFFFFFEull;          // the prefix rows are uint32: a scaffold of 2^31 - 1 characters or more is refused
 constexpr uint64_t MAX_WINDOWS = 0x7FFFFFFFull;
-constexpr int NKMER = sw::NKMER;
+using ckm::NKMER;
 constexpr int NTOTALS = 2 + NKMER;                         // gc, at, the 136 canonical columns
 constexpr uint32_t TD_ROW_BYTES = NKMER * 4;
 

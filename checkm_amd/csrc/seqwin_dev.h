@@ -23,11 +23,11 @@
 namespace ckm {
 namespace sw {
 
-constexpr int LANE_BYTES = 16;
-constexpr int WAVE = 64;
-constexpr int WAVE_BYTES = LANE_BYTES * WAVE;
+using ckm::LANE_BYTES;
+using ckm::WAVE;
+using ckm::WAVE_BYTES;
 constexpr int HALO = 3;                          // bytes after the chunk a lane looks at: the rest of a 4-mer
-constexpr int NKMER = ns::NKMER;
+using ckm::NKMER;
 constexpr uint32_t ROW_BYTES = NKMER * 4;        // a window's 136 uint32 counts: scratch of a batch, never kept
 constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
 constexpr uint32_t MIN_PIECE = 16, DEFAULT_PIECE = 4096;

@@ -9,6 +9,7 @@
 #pragma once
 #include <cstdint>
 #include <vector>
+#include "wave_const.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define UB_HD __host__ __device__ __forceinline__
@@ -19,9 +20,9 @@
 namespace ckm {
 namespace ub {
 
-constexpr int LANE_BYTES = 16;
-constexpr int WAVE = 64;
-constexpr int WAVE_BYTES = LANE_BYTES * WAVE;
+using ckm::LANE_BYTES;
+using ckm::WAVE;
+using ckm::WAVE_BYTES;
 constexpr int NCOUNT = 5;                         // A, C, G, T+U, code points
 constexpr uint32_t DEFAULT_TILE = 4096, MAX_TILE = 1u << 20;
 constexpr uint32_t HI = 0x80808080u;
