@@ -186,6 +186,13 @@ class AaiColumns(C.Structure):
                [(f, C.c_double) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")]
 
 
+class MsetColumns(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("nqueries", "nfamilies", "npairs", "nbatches", "nrounds", "tests")] + \
+               [("flag", C.POINTER(C.c_uint8)), ("counts", C.POINTER(C.c_uint32)), ("pair_off", C.POINTER(C.c_uint64)),
+                ("i", C.POINTER(C.c_uint32)), ("j", C.POINTER(C.c_uint32)), ("count", C.POINTER(C.c_uint32))] + \
+               [(f, C.c_double) for f in ("ms_upload", "ms_markers", "ms_pack", "ms_count", "ms_scan", "ms_fill", "ms_download", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -223,6 +230,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_refdist_check", "ckm_refdist_run", "ckm_refdist_coding",
            "ckm_fasta_ids_read", "ckm_fasta_ids_view_get", "ckm_fasta_ids_free", "ckm_unbinned_select", "ckm_unbinned_count", "ckm_unbinned_write",
            "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
+           "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -345,6 +353,16 @@ def load():
     L.ckm_aai_columns_get.argtypes = [C.c_void_p, C.POINTER(AaiColumns)]
     L.ckm_aai_free.argtypes = [C.c_void_p]
     L.ckm_aai_free.restype = None
+    L.ckm_mset_check.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double]
+    L.ckm_mset_table_create.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_void_p)]
+    L.ckm_mset_table_free.argtypes = [C.c_void_p]
+    L.ckm_mset_table_free.restype = None
+    L.ckm_mset_markers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_void_p)]
+    L.ckm_mset_colocated.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_uint64,
+                                     C.POINTER(C.c_void_p)]
+    L.ckm_mset_columns_get.argtypes = [C.c_void_p, C.POINTER(MsetColumns)]
+    L.ckm_mset_result_free.argtypes = [C.c_void_p]
+    L.ckm_mset_result_free.restype = None
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1363,4 +1381,121 @@ def aai_pairs(ctx, groups, budget_bytes=0):
             out[f] = getattr(c, f)
     finally:
         load().ckm_aai_free(h)
+    return out
+
+
+def _mset_table_args(count_class, pos_off, pos):
+    """(ngenomes, nfamilies, classes uint8 [G, C], pos_off uint64 [G * C + 1], pos int64) of a table given as arrays."""
+    cls = np.ascontiguousarray(count_class, dtype=np.uint8)
+    if cls.ndim != 2:
+        raise ValueError("count_class must be [ngenomes, nfamilies]")
+    off = np.ascontiguousarray(pos_off, dtype=np.uint64).reshape(-1)
+    if off.shape[0] != cls.shape[0] * cls.shape[1] + 1:
+        raise ValueError("pos_off must hold ngenomes * nfamilies + 1 entries")
+    return cls.shape[0], cls.shape[1], cls, off, np.ascontiguousarray(pos, dtype=np.int64).reshape(-1)
+
+
+def _mset_lists(lists):
+    """(offsets uint64 [n + 1], members uint32) of a sequence of index lists."""
+    off = np.zeros(len(lists) + 1, dtype=np.uint64)
+    np.cumsum([len(x) for x in lists], out=off[1:])
+    flat = np.concatenate([np.asarray(x, dtype=np.int64).reshape(-1) for x in lists]) if len(lists) else np.zeros(0, dtype=np.int64)
+    if flat.size and (flat.min() < 0 or flat.max() > 0xFFFFFFFF):
+        raise CkmError(-1, "an index that does not fit uint32")
+    return off, np.ascontiguousarray(flat, dtype=np.uint32)
+
+
+def _ptr(a):
+    return a.ctypes.data if a.size else None
+
+
+def mset_check(count_class, pos_off, pos, genome_lists=None, marker_lists=None, dist_threshold=5000):
+    """ckm_mset_check: why a table, the queries of a call or a distance threshold would be refused, without a device.  Raises CkmError
+    as MsetTable / mset_markers / mset_colocated would."""
+    G, Cn, cls, off, p = _mset_table_args(count_class, pos_off, pos)
+    goff, g = _mset_lists(genome_lists) if genome_lists is not None else (None, None)
+    moff, m = _mset_lists(marker_lists) if marker_lists is not None else (None, None)
+    _chk(load().ckm_mset_check(G, Cn, _ptr(cls), off.ctypes.data, _ptr(p), len(genome_lists) if genome_lists is not None else 0,
+                               goff.ctypes.data if goff is not None else None, _ptr(g) if g is not None else None,
+                               moff.ctypes.data if moff is not None else None, _ptr(m) if m is not None else None, float(dist_threshold)))
+
+
+class MsetTable(object):
+    """The resident table of MarkerSetBuilder (ckm_mset_table_create): count_class [ngenomes, nfamilies] of 0 / 1 / 2, and the copy
+    positions of every (genome, family) cell as pos[pos_off[cell] : pos_off[cell + 1]], cells genome-major."""
+
+    def __init__(self, ctx, count_class, pos_off, pos):
+        self.ngenomes, self.nfamilies, cls, off, p = _mset_table_args(count_class, pos_off, pos)
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        ms = C.c_double(0.0)
+        _chk(load().ckm_mset_table_create(ctx.h, self.ngenomes, self.nfamilies, _ptr(cls), off.ctypes.data, _ptr(p), C.byref(ms), C.byref(self.h)))
+        self.ms_upload = ms.value
+
+    def close(self):
+        if self.h:
+            load().ckm_mset_table_free(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # interpreter shutdown: the library may be gone already
+            pass
+
+
+_MSET_MS = ("ms_upload", "ms_markers", "ms_pack", "ms_count", "ms_scan", "ms_fill", "ms_download", "ms_total")
+
+
+def mset_markers(ctx, table, genome_lists, ubiquity_thresholds, single_copy_thresholds, want_counts=False, budget_bytes=0):
+    """The marker pass (ckm_mset_markers) over a batch of queries: genome_lists are lists of genome indices of the table, the thresholds
+    the doubles the caller computed.  Returns a dict: flag [nqueries, nfamilies] uint8 (bit 0 marker, bit 1 missing, bit 2 duplicate),
+    counts [nqueries, nfamilies, 3] uint32 (ubiquity, single, duplicate) or None, nbatches and the timings in ms."""
+    goff, g = _mset_lists(genome_lists)
+    tu = np.ascontiguousarray(ubiquity_thresholds, dtype=np.float64).reshape(-1)
+    ts = np.ascontiguousarray(single_copy_thresholds, dtype=np.float64).reshape(-1)
+    nq = len(genome_lists)
+    if tu.shape[0] != nq or ts.shape[0] != nq:
+        raise ValueError("one threshold pair per query")
+    h = C.c_void_p()
+    _chk(load().ckm_mset_markers(ctx.h, table.h, nq, goff.ctypes.data, _ptr(g), _ptr(tu), _ptr(ts), 1 if want_counts else 0, int(budget_bytes), C.byref(h)))
+    try:
+        c = MsetColumns()
+        _chk(load().ckm_mset_columns_get(h, C.byref(c)))
+        n = nq * table.nfamilies
+        arr = np.ctypeslib.as_array
+        out = dict(nbatches=int(c.nbatches), flag=(arr(c.flag, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint8)).reshape(nq, table.nfamilies), counts=None)
+        if want_counts:
+            out["counts"] = (arr(c.counts, shape=(n * 3,)).copy() if n else np.zeros(0, dtype=np.uint32)).reshape(nq, table.nfamilies, 3)
+        for f in _MSET_MS:
+            out[f] = getattr(c, f)
+    finally:
+        load().ckm_mset_result_free(h)
+    return out
+
+
+def mset_colocated(ctx, table, genome_lists, marker_lists, dist_threshold=5000, genome_threshold=0.95, budget_bytes=0):
+    """The co-location pass (ckm_mset_colocated) over a batch of queries: per query a list of genome indices and a list of family indices
+    (its markers).  Returns a dict: pair_off [nqueries + 1] uint64 and per reported pair, in ascending (i, j) per query, i and j
+    (positions in the query's marker list) and count (genomes), uint32; npairs, nbatches, nrounds, tests and the timings in ms."""
+    if len(genome_lists) != len(marker_lists):
+        raise ValueError("one marker list per query")
+    goff, g = _mset_lists(genome_lists)
+    moff, m = _mset_lists(marker_lists)
+    nq = len(genome_lists)
+    h = C.c_void_p()
+    _chk(load().ckm_mset_colocated(ctx.h, table.h, nq, goff.ctypes.data, _ptr(g), moff.ctypes.data, _ptr(m), float(dist_threshold), float(genome_threshold),
+                                   int(budget_bytes), C.byref(h)))
+    try:
+        c = MsetColumns()
+        _chk(load().ckm_mset_columns_get(h, C.byref(c)))
+        k = int(c.npairs)
+        arr = np.ctypeslib.as_array
+        out = dict(npairs=k, nbatches=int(c.nbatches), nrounds=int(c.nrounds), tests=int(c.tests), pair_off=arr(c.pair_off, shape=(nq + 1,)).copy())
+        for f in ("i", "j", "count"):
+            out[f] = arr(getattr(c, f), shape=(k,)).copy() if k else np.zeros(0, dtype=np.uint32)
+        for f in _MSET_MS:
+            out[f] = getattr(c, f)
+    finally:
+        load().ckm_mset_result_free(h)
     return out

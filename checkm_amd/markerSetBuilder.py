@@ -1,0 +1,330 @@
+"""MarkerSetBuilder, with the results of scripts/genometreeworkflow/markerSetBuilder.py of the reference for markerGenes (:131-157),
+colocatedGenes (:159-192), colocatedSets (:194-235), genomeCheck (:237-263), missingGenes (:486-510), duplicateGenes (:512-536),
+buildMarkerGenes (:538-562) and buildMarkerSet (:564-574), and one method the reference lacks: buildMarkerSets answers a whole batch of
+genome sets -- every node of a tree -- from ONE table resident on the device, with two device calls.
+
+The counting loops run in libcheckm_hip (checkm_amd/csrc/kernels_markerset.hip): the marker pass gives one flag byte per (query,
+family), the co-location pass the reported marker pairs of every query.  colocatedSets is a union-find on the host, genomeCheck host
+float arithmetic in the reference's order.  What the library refuses -- a position that does not fit int32, a distThreshold that is
+not an integer, a genome listed twice in a query -- runs this module's own plain loop at that place.  Without a device the device
+methods raise: there is no other compute path.
+
+The reference's lists came out in the order of Python 2's dicts.  Here they are defined: colocatedGenes returns its pair strings
+sorted, colocatedSets its sets sorted by their smallest member.  Equality with the reference is equality of sets.  DESIGN section 21.
+
+The simulation and tree-walking methods of the script (sampleGenome*, buildBinMarkerSet, ...) are not here."""
+from collections import defaultdict
+import logging
+import time
+
+import numpy as np
+
+from checkm_amd.markerSets import MarkerSet
+
+
+def _pair_name(a, b):
+    return a + '-' + b if a <= b else b + '-' + a
+
+
+def _count_class(c):
+    return 1 if c == 1 else 2 if c > 1 else 0
+
+
+class _Resident(object):
+    """The table as arrays: families sorted by name, genomes in the given order, count classes genome-major, and the copy positions of
+    every (genome, family) cell.  `device()` is the library's copy of it, made on first use."""
+
+    def __init__(self, genomeIds, countTable, positions=None, families=None):
+        self.genomes = list(genomeIds)
+        self.gidx = {g: k for k, g in enumerate(self.genomes)}
+        self.families = sorted(countTable) if families is None else list(families)
+        self.fidx = {f: k for k, f in enumerate(self.families)}
+        G, C = len(self.genomes), len(self.families)
+        self.cls = np.zeros((G, C), dtype=np.uint8)
+        if countTable is not None:
+            for f, fam in enumerate(self.families):
+                for g, c in countTable[fam].items():
+                    k = self.gidx.get(g)
+                    if k is not None:
+                        self.cls[k, f] = _count_class(c)
+        ncopies = np.zeros((G, C), dtype=np.int64)
+        starts = []
+        for g, genome in enumerate(self.genomes):
+            here = (positions or {}).get(genome) or {}
+            mine = sorted((self.fidx[fam], copies) for fam, copies in here.items() if fam in self.fidx)
+            for f, copies in mine:
+                ncopies[g, f] = len(copies)
+                starts.extend(p[0] for p in copies)
+        self.pos_off = np.zeros(G * C + 1, dtype=np.uint64)
+        np.cumsum(ncopies.reshape(-1), out=self.pos_off[1:])
+        self.integral = all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in starts)
+        self.fits = self.integral and all(-(1 << 63) <= s < (1 << 63) for s in starts)
+        self.pos = np.asarray(starts, dtype=np.int64) if self.fits else np.zeros(0, dtype=np.int64)
+        self._table = None
+
+    def refused(self, dist_threshold=0):
+        """Why the library would not take this table (or this threshold), or None.  ckm_mset_check, no device."""
+        from checkm_amd import _lib
+        if not self.fits:
+            return 'a position that is not an integer of 64 bits'
+        try:
+            _lib.mset_check(self.cls, self.pos_off, self.pos, dist_threshold=dist_threshold)
+        except _lib.CkmError as e:
+            return str(e)
+        return None
+
+    def device(self, timing=None):
+        if self._table is None:
+            from checkm_amd import _lib, runtime
+            self._table = _lib.MsetTable(runtime.get_ctx(), self.cls, self.pos_off, self.pos)
+            if timing is not None:
+                timing['copy_in'] += self._table.ms_upload / 1e3
+        return self._table
+
+    def close(self):
+        if self._table is not None:
+            self._table.close()
+            self._table = None
+
+
+def _integral(x):
+    try:
+        return float(x) == int(x)
+    except (TypeError, ValueError, OverflowError):
+        return False
+
+
+class MarkerSetBuilder(object):
+    def __init__(self, img=None):
+        self.logger = logging.getLogger('timestamp')
+        self.img = img
+        self.cachedGeneCountTable = None
+        self.last_timing = {}
+
+    def precomputeGenomeSeqLens(self, genomeIds):
+        self.img.precomputeGenomeSeqLens(genomeIds)
+
+    def precomputeGenomeFamilyPositions(self, genomeIds, spacingBetweenContigs):
+        self.img.precomputeGenomeFamilyPositions(genomeIds, spacingBetweenContigs)
+
+    # ---- the marker pass ------------------------------------------------------------------------------------------------------------
+    def _ctx(self):
+        from checkm_amd import runtime
+        return runtime.get_ctx()
+
+    @staticmethod
+    def _walk(genomeIds, genomeCounts):
+        """One family of one query on the host: ubiquity, single-copy and duplicate counts."""
+        ubiquity = single = duplicate = 0
+        for genomeId in genomeIds:
+            c = genomeCounts.get(genomeId, 0)
+            ubiquity += c > 0
+            single += c == 1
+            duplicate += c > 1
+        return ubiquity, single, duplicate
+
+    def _flags(self, genomeIds, countTable, tU, tS):
+        """family -> flag byte of the marker pass for ONE query; the plain loop for a genome list the library does not take.  With a
+        genome listed twice ubiquity can exceed len(genomeCounts), and only then does the reference's early `continue` decide."""
+        genomeIds = list(genomeIds)
+        if len(set(genomeIds)) != len(genomeIds):
+            out = {}
+            for fam, genomeCounts in countTable.items():
+                u, s, d = self._walk(genomeIds, genomeCounts)
+                out[fam] = (1 if len(genomeCounts) >= tU and u >= tU and s >= tS else 0) | (2 if len(genomeIds) - u >= tU else 0) | (4 if d >= tU else 0)
+            return out
+        from checkm_amd import _lib
+        res = _Resident(genomeIds, countTable)
+        try:
+            r = _lib.mset_markers(self._ctx(), res.device(), [list(range(len(genomeIds)))], [tU], [tS])
+        finally:
+            res.close()
+        return dict(zip(res.families, r['flag'][0].tolist()))
+
+    def markerGenes(self, genomeIds, countTable, ubiquityThreshold, singleCopyThreshold):
+        """Families present in at least ubiquityThreshold and single-copy in at least singleCopyThreshold of the genomes (both are
+        numbers of genomes).  The reference's early `continue` on len(genomeCounts) is not reproduced: it never changes a result."""
+        if ubiquityThreshold < 1 or singleCopyThreshold < 1:
+            print('[Warning] Looks like degenerate threshold.')
+        flags = self._flags(genomeIds, countTable, float(ubiquityThreshold), float(singleCopyThreshold))
+        return set(fam for fam, f in flags.items() if f & 1)
+
+    def _count_table(self, genomeIds):
+        return self.cachedGeneCountTable if self.cachedGeneCountTable is not None else self.img.geneCountTable(genomeIds)
+
+    def missingGenes(self, genomeIds, markerGenes, ubiquityThreshold):
+        """Markers absent from at least ubiquityThreshold * len(genomeIds) of the genomes."""
+        t = ubiquityThreshold * len(genomeIds)
+        flags = self._flags(genomeIds, self._count_table(genomeIds), float(t), 0.0)
+        return set(fam for fam, f in flags.items() if f & 2 and fam in markerGenes)
+
+    def duplicateGenes(self, genomeIds, markerGenes, ubiquityThreshold):
+        """Markers with more than one copy in at least ubiquityThreshold * len(genomeIds) of the genomes."""
+        t = ubiquityThreshold * len(genomeIds)
+        flags = self._flags(genomeIds, self._count_table(genomeIds), float(t), 0.0)
+        return set(fam for fam, f in flags.items() if f & 4 and fam in markerGenes)
+
+    def buildMarkerGenes(self, genomeIds, ubiquityThreshold, singleCopyThreshold):
+        markers = self.markerGenes(genomeIds, self._count_table(genomeIds), ubiquityThreshold * len(genomeIds), singleCopyThreshold * len(genomeIds))
+        return markers - self.img.identifyRedundantTIGRFAMs(markers)
+
+    # ---- the co-location pass ---------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _colocated_host(geneDistTable, distThreshold, genomeThreshold):
+        """The reference's loop, plainly: per genome every pair of its families, any two copies closer than the threshold."""
+        seen = defaultdict(int)
+        for locs in geneDistTable.values():
+            ids = list(locs)
+            for a in range(len(ids)):
+                for b in range(a + 1, len(ids)):
+                    if any(abs(p[0] - q[0]) < distThreshold for p in locs[ids[a]] for q in locs[ids[b]]):
+                        seen[_pair_name(ids[a], ids[b])] += 1
+        return sorted(name for name, count in seen.items() if float(count) / len(geneDistTable) > genomeThreshold)
+
+    def colocatedGenes(self, geneDistTable, distThreshold=5000, genomeThreshold=0.95):
+        """'A-B' (A <= B) for every pair of families with copies closer than distThreshold in more than genomeThreshold of the genomes
+        of geneDistTable; sorted."""
+        genomes = list(geneDistTable)
+        families = sorted(set(fam for locs in geneDistTable.values() for fam in locs))
+        if not genomes or len(families) < 2:
+            return []
+        res = None
+        if _integral(distThreshold):
+            res = _Resident(genomes, None, geneDistTable, families)
+            if res.refused(int(distThreshold)) is not None:
+                res = None
+        if res is None:
+            return self._colocated_host(geneDistTable, distThreshold, genomeThreshold)
+        from checkm_amd import _lib
+        try:
+            r = _lib.mset_colocated(self._ctx(), res.device(), [list(range(len(genomes)))], [list(range(len(families)))], int(distThreshold), float(genomeThreshold))
+        finally:
+            res.close()
+        return sorted(_pair_name(families[i], families[j]) for i, j in zip(r['i'].tolist(), r['j'].tolist()))
+
+    def colocatedSets(self, colocatedGenes, markerGenes):
+        """The connected groups of the pairs, and every marker outside them by itself; sorted by the smallest member."""
+        parent = {}
+
+        def root(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for cg in colocatedGenes:
+            geneA, geneB = cg.split('-')
+            ra, rb = root(parent.setdefault(geneA, geneA)), root(parent.setdefault(geneB, geneB))
+            if ra != rb:
+                parent[max(ra, rb)] = min(ra, rb)
+        groups = defaultdict(set)
+        for gene in parent:
+            groups[root(gene)].add(gene)
+        sets = list(groups.values()) + [set([m]) for m in markerGenes if m not in parent]
+        return sorted(sets, key=min)
+
+    def genomeCheck(self, colocatedSet, genomeId, countTable):
+        """Completeness and contamination of one genome as fractions, and its missing and duplicated markers."""
+        comp = cont = 0.0
+        missingMarkers, duplicateMarkers = set(), set()
+        if len(colocatedSet) == 0:
+            return comp, cont, missingMarkers, duplicateMarkers
+        for cs in colocatedSet:
+            present = multiCopy = 0
+            for marker in cs:
+                count = countTable[marker].get(genomeId, 0)
+                if count == 1:
+                    present += 1
+                elif count > 1:
+                    present += 1
+                    multiCopy += count - 1
+                    duplicateMarkers.add(marker)
+                elif count == 0:
+                    missingMarkers.add(marker)
+            comp += float(present) / len(cs)
+            cont += float(multiCopy) / len(cs)
+        return comp / len(colocatedSet), cont / len(colocatedSet), missingMarkers, duplicateMarkers
+
+    # ---- whole marker sets ------------------------------------------------------------------------------------------------------------
+    def buildMarkerSet(self, genomeIds, ubiquityThreshold, singleCopyThreshold, spacingBetweenContigs=5000):
+        return self.buildMarkerSets([genomeIds], ubiquityThreshold, singleCopyThreshold, spacingBetweenContigs)[0]
+
+    def _marker_set_host(self, genomeIds, table, positions, ubiquityThreshold, singleCopyThreshold):
+        """One query entirely on the plain loops."""
+        n = len(genomeIds)
+        tU, tS = ubiquityThreshold * n, singleCopyThreshold * n
+        markers = set()
+        for fam, genomeCounts in table.items():
+            u, s, _d = self._walk(genomeIds, genomeCounts)
+            if len(genomeCounts) >= tU and u >= tU and s >= tS:
+                markers.add(fam)
+        markers -= self.img.identifyRedundantTIGRFAMs(markers)
+        dist = {g: {m: positions[g][m] for m in markers if m in positions[g]} for g in genomeIds}
+        return markers, self._colocated_host(dist, 5000, 0.95)
+
+    def buildMarkerSets(self, listOfGenomeIdLists, ubiquityThreshold, singleCopyThreshold, spacingBetweenContigs=5000):
+        """[buildMarkerSet(ids, ...) for ids in listOfGenomeIdLists] from one resident table: the marker pass over all lists in one
+        device call, the TIGRFAM redundancy removal per list on the host, the co-location pass over all lists in a second call.  The
+        gene count table is cachedGeneCountTable if set, else img.geneCountTable of the genomes of all lists together: a family
+        absent from the genomes of a list has ubiquity 0 there, so with thresholds above zero the markers of a list are those of its
+        own table."""
+        t = dict(read=0.0, table=0.0, copy_in=0.0, markers=0.0, pack=0.0, count=0.0, scan=0.0, fill=0.0, copy_out=0.0, union_find=0.0, python=0.0,
+                 queries=len(listOfGenomeIdLists), pairs=0, tests=0, rounds=0, batches=0)
+        self.last_timing = t
+        t_begin = time.perf_counter()
+        lists = [list(ids) for ids in listOfGenomeIdLists]
+        allGenomes = sorted(set(g for ids in lists for g in ids))
+        t0 = time.perf_counter()
+        table = self._count_table(allGenomes)
+        positions = self.img.geneDistTable(allGenomes, list(table), spacingBetweenContigs)
+        t['read'] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        res = _Resident(allGenomes, table, positions)
+        refused = res.refused(5000)
+        t['table'] = time.perf_counter() - t0
+        # the lists the library takes: no genome twice (the table itself may be refused as a whole)
+        device = [k for k, ids in enumerate(lists) if refused is None and len(set(ids)) == len(ids)]
+        markers, pairs = {}, {}
+        try:
+            self._device_passes(res, lists, device, ubiquityThreshold, singleCopyThreshold, markers, pairs, t)
+        finally:
+            res.close()
+        out = []
+        for k, ids in enumerate(lists):
+            if ubiquityThreshold * len(ids) < 1 or singleCopyThreshold * len(ids) < 1:
+                print('[Warning] Looks like degenerate threshold.')
+            if k not in markers:
+                markers[k], pairs[k] = self._marker_set_host(ids, table, positions, ubiquityThreshold, singleCopyThreshold)
+            t0 = time.perf_counter()
+            sets = self.colocatedSets(pairs[k], markers[k])
+            t['union_find'] += time.perf_counter() - t0
+            out.append(MarkerSet(0, 'NA', len(ids), sets))
+        t['python'] = time.perf_counter() - t_begin - sum(t[k] for k in ('read', 'table', 'copy_in', 'markers', 'pack', 'count', 'scan', 'fill', 'copy_out', 'union_find'))
+        return out
+
+    def _device_passes(self, res, lists, device, ubiquityThreshold, singleCopyThreshold, markers, pairs, t):
+        """The two device calls of buildMarkerSets over the lists numbered in `device`; fills markers[k] and pairs[k]."""
+        from checkm_amd import _lib
+        if device:
+            ctx = self._ctx()
+            dev = res.device(t)
+            glists = [[res.gidx[g] for g in lists[k]] for k in device]
+            r = _lib.mset_markers(ctx, dev, glists, [ubiquityThreshold * len(lists[k]) for k in device], [singleCopyThreshold * len(lists[k]) for k in device])
+            t['copy_in'] += r['ms_upload'] / 1e3
+            t['markers'] += r['ms_markers'] / 1e3
+            t['copy_out'] += r['ms_download'] / 1e3
+            fams = np.asarray(res.families, dtype=object)
+            mlists = []
+            for row, k in enumerate(device):
+                found = set(fams[np.nonzero(r['flag'][row] & 1)[0]].tolist())
+                found -= self.img.identifyRedundantTIGRFAMs(found)
+                markers[k] = found
+                mlists.append(sorted(res.fidx[m] for m in found))
+            r = _lib.mset_colocated(ctx, dev, glists, mlists, 5000, 0.95)
+            for name, key in (('copy_in', 'ms_upload'), ('pack', 'ms_pack'), ('count', 'ms_count'), ('scan', 'ms_scan'), ('fill', 'ms_fill'), ('copy_out', 'ms_download')):
+                t[name] += r[key] / 1e3
+            t['pairs'], t['tests'], t['rounds'], t['batches'] = int(r['npairs']), int(r['tests']), int(r['nrounds']), int(r['nbatches'])
+            off, pi, pj = r['pair_off'].tolist(), r['i'].tolist(), r['j'].tolist()
+            for row, k in enumerate(device):
+                ml = mlists[row]
+                pairs[k] = sorted(_pair_name(res.families[ml[pi[x]]], res.families[ml[pj[x]]]) for x in range(off[row], off[row + 1]))

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12 */
 
 enum {
   CKM_OK      =  0,
@@ -693,6 +693,66 @@ int  ckm_aai_check(uint32_t ngroups, const uint64_t *group_row_off, const uint64
 int  ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group_row_off, const uint64_t *row_off, const char *text, uint64_t budget_bytes, ckm_aai **out);
 int  ckm_aai_columns_get(const ckm_aai *r, ckm_aai_columns *out);
 void ckm_aai_free(ckm_aai *r);
+
+/* ---- MarkerSetBuilder: marker genes and co-located marker pairs of a batch of genome sets (additions to ABI 12) --------------
+ * Replaces the loops of scripts/genometreeworkflow/markerSetBuilder.py: markerGenes (:131-157), missingGenes (:486-510), duplicateGenes
+ * (:512-536) and colocatedGenes (:159-192).  checkm_amd/csrc/markerset_dev.h, kernels_markerset.hip.
+ *
+ * The table, for ngenomes genomes and nfamilies families, genome-major: count_class[g * nfamilies + f] = 0, 1 or 2 (more than one) is the
+ * class of geneCountTable[f].get(g, 0); the start positions of the copies of f in g (the first number of every entry of
+ * IMG._genomeFamilyPositions(g)[f], checkm/util/img.py:420-490, contigs laid end to end) are pos[pos_off[g * nfamilies + f] ..
+ * pos_off[g * nfamilies + f + 1] - 1]; pos_off holds ngenomes * nfamilies + 1 entries, starts at 0 and never falls.  Class and copies are
+ * independent of each other.  ckm_mset_table_create copies the table to the device (positions as int32), where it stays until
+ * ckm_mset_table_free; ms_upload (may be NULL) receives the milliseconds of the copy.
+ *
+ * A query is a list of genomes: qg[qg_off[q] .. qg_off[q + 1] - 1], indices into the table (qg_off holds nqueries + 1 entries from 0).
+ *
+ * ckm_mset_markers (markerGenes :138-155): per query and family, over the query's n genomes, ubiquity = genomes of class > 0, single =
+ * genomes of class 1, duplicate = genomes of class 2, and one flag byte flag[q * nfamilies + f]:
+ *   bit 0  (double)ubiquity >= ubiquity_threshold[q] && (double)single >= single_copy_threshold[q]      the family is a marker (:154)
+ *   bit 1  (double)(n - ubiquity) >= ubiquity_threshold[q]                                                missingGenes (:507)
+ *   bit 2  (double)duplicate >= ubiquity_threshold[q]                                                     duplicateGenes (:533)
+ * The thresholds are the doubles the caller computed (ubiquityThreshold * len(genomeIds), ...).  want_counts != 0: counts[(q * nfamilies
+ * + f) * 3 ..] = ubiquity, single, duplicate.  The reference's early `continue` (:141) never changes a result and is not reproduced
+ * (DESIGN §21).  A genome listed twice in a query counts twice, as in the reference's loop.
+ *
+ * ckm_mset_colocated (colocatedGenes :163-190): a query also has a marker list qm[qm_off[q] .. qm_off[q + 1] - 1] of family indices.  For
+ * every pair i < j of positions of that list, count = the query's genomes in which both families have a copy and some pair of copies has
+ * |start1 - start2| < dist_threshold; the pair is reported when (double)count / (double)n > genome_threshold (:189; one IEEE division;
+ * n = the genomes of the query, also those without any marker).  Reported pairs of query q are pair_off[q] .. pair_off[q + 1] - 1, in
+ * ascending (i, j): i[], j[] are positions in the query's marker list, count[] the genomes.  A query without a genome or with fewer than
+ * two markers reports nothing.  The pass runs in rounds of whole queries and its output in batches of whole rows, both within
+ * budget_bytes (0: CKM_MSET_BATCH_MB, default 256, << 20; a round holds at least one query, a batch at least one row); neither changes
+ * a result.  A call without a pair to test does not touch the device.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, an offset table that does not start at 0 or falls, a class above 2, an
+ * index beyond the table, a dist_threshold that is not an integer; CKM_ERANGE for a position outside [0, 2^31), a dist_threshold outside
+ * [0, 2^31), more than 2^31 - 1 positions, more than 2^24 genomes or families, more than 2^40 cells, more than 2^20 markers in a query.
+ * ckm_mset_check applies the same tests (the query tables when qg_off is not NULL, the marker lists when qm_off is not NULL) and needs
+ * no device: the caller then computes such a table or call with its own loop. */
+typedef struct ckm_mset_table ckm_mset_table;
+typedef struct ckm_mset_result ckm_mset_result;
+typedef struct {
+  uint64_t        nqueries, nfamilies;
+  uint64_t        npairs, nbatches, nrounds;  /* reported pairs; output batches (marker pass: launches); rounds of the co-location pass */
+  uint64_t        tests;                      /* (genome, pair) tests of the co-location pass: sum of n * m (m - 1) / 2 */
+  const uint8_t  *flag;                       /* marker pass: [nqueries * nfamilies] */
+  const uint32_t *counts;                     /* marker pass with want_counts: [nqueries * nfamilies * 3], else NULL */
+  const uint64_t *pair_off;                   /* co-location pass: [nqueries + 1] */
+  const uint32_t *i, *j, *count;              /* co-location pass: [npairs] */
+  double          ms_upload, ms_markers, ms_pack, ms_count, ms_scan, ms_fill, ms_download, ms_total;   /* HIP events per phase; wall of the call */
+} ckm_mset_columns;
+int  ckm_mset_check(uint32_t ngenomes, uint32_t nfamilies, const uint8_t *count_class, const uint64_t *pos_off, const int64_t *pos, uint32_t nqueries,
+                    const uint64_t *qg_off, const uint32_t *qg, const uint64_t *qm_off, const uint32_t *qm, double dist_threshold);
+int  ckm_mset_table_create(ckm_ctx *ctx, uint32_t ngenomes, uint32_t nfamilies, const uint8_t *count_class, const uint64_t *pos_off, const int64_t *pos,
+                           double *ms_upload, ckm_mset_table **out);
+void ckm_mset_table_free(ckm_mset_table *t);
+int  ckm_mset_markers(ckm_ctx *ctx, const ckm_mset_table *t, uint32_t nqueries, const uint64_t *qg_off, const uint32_t *qg, const double *ubiquity_threshold,
+                      const double *single_copy_threshold, int want_counts, uint64_t budget_bytes, ckm_mset_result **out);
+int  ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_t nqueries, const uint64_t *qg_off, const uint32_t *qg, const uint64_t *qm_off,
+                        const uint32_t *qm, double dist_threshold, double genome_threshold, uint64_t budget_bytes, ckm_mset_result **out);
+int  ckm_mset_columns_get(const ckm_mset_result *r, ckm_mset_columns *out);
+void ckm_mset_result_free(ckm_mset_result *r);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
