@@ -11,6 +11,7 @@
 #include <vector>
 #include "ckm_host.h"
 #include "markerset_dev.h"
+#include "pairs_host.h"
 
 namespace ckm {
 struct MsetTableDev { const uint8_t *cls; const uint32_t *pos_off; const int32_t *pos; uint32_t G, C; };
@@ -157,23 +158,25 @@ extern "C" int ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_
     if (work) {
       cs.open(ctx->device);
       const MsetTableDev T = t->dev();
-      DevBuf d_g, d_m, d_q, d_tiles, d_pk, d_cnt, d_total, d_base, d_out;
-      PinnedBuf h_out;
+      DevBuf d_g, d_m, d_q, d_tiles, d_pk, d_cnt;
+      PairBatches pb;
       cs.timed(o->ms_upload, [&] {
         put(cs, d_g, qg, qg_off[nqueries] * 4);
         put(cs, d_m, qm, qm_off[nqueries] * 4);
       });
       ms::Round R;
-      std::vector<uint32_t> row_total;
-      std::vector<uint64_t> row_base;
-      std::vector<ms::Group> groups;
+      auto take = [&](const void *h_out, uint64_t n) {
+        const uint32_t *hi = static_cast<const uint32_t *>(h_out);
+        o->pi.insert(o->pi.end(), hi, hi + n); o->pj.insert(o->pj.end(), hi + n, hi + 2 * n); o->count.insert(o->count.end(), hi + 2 * n, hi + 3 * n);
+        o->npairs += n; o->nbatches += 1;
+      };
       for (uint32_t q0 = 0; q0 < nqueries;) {
         const uint32_t q1 = ms::next_round(nqueries, qg_off, qm_off, budget_bytes, q0);
         ms::build_round(qg_off, qm_off, q0, q1, R);
         const uint32_t nq = q1 - q0, nrows = R.rows, ntiles = (uint32_t)R.tiles.size();
         if (ntiles) {
           o->nrounds += 1;
-          d_pk.ensure(R.entries * sizeof(ms::Entry)); d_cnt.ensure(R.counts * 4); d_total.ensure((size_t)nrows * 4); d_base.ensure((size_t)nrows * 8);
+          d_pk.ensure(R.entries * sizeof(ms::Entry)); d_cnt.ensure(R.counts * 4);
           cs.timed(o->ms_upload, [&] {
             put(cs, d_q, R.queries.data(), (size_t)nq * sizeof(ms::Query));
             put(cs, d_tiles, R.tiles.data(), (size_t)ntiles * sizeof(ms::Tile));
@@ -187,42 +190,24 @@ extern "C" int ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_
                               d_cnt.as<uint32_t>(), none);
             HIPCHK(hipGetLastError());
           });
-          row_total.resize(nrows); row_base.resize(nrows);
-          cs.timed(o->ms_scan, [&] {
-            launch_mset_scan(cs.st, dq, nq, nrows, d_cnt.as<uint32_t>(), d_total.as<uint32_t>());
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(row_total.data(), d_total.p, (size_t)nrows * 4, hipMemcpyDeviceToHost, cs.st));
-          });
+          pb.run(cs, 0, nrows, cap_pairs, ms::PAIR_BYTES, o->ms_scan, o->ms_fill, o->ms_download,
+                 [&](uint32_t *d_total) { launch_mset_scan(cs.st, dq, nq, nrows, d_cnt.as<uint32_t>(), d_total); },
+                 [&](const pc::Group &g, void *d_out, uint64_t n) {
+                   uint32_t *di = static_cast<uint32_t *>(d_out);
+                   const MsetOut mo = {pb.d_base.as<uint64_t>(), pb.d_total.as<uint32_t>(), g.base, n, di, di + n, di + 2 * n};
+                   const ms::TileRange tr = ms::tile_range(g, R.tiles);
+                   launch_mset_tiles(cs.st, true, T, dq, dt, tr.t_lo, tr.t_hi, d_g.as<uint32_t>(), d_m.as<uint32_t>(), d_pk.as<ms::Entry>(), D, genome_threshold, g.row_lo, g.row_hi,
+                                     d_cnt.as<uint32_t>(), mo);
+                 },
+                 take);
           const auto s0 = std::chrono::steady_clock::now();
-          uint64_t run = 0;
-          for (uint32_t k = 0; k < nrows; ++k) { row_base[k] = run; run += row_total[k]; }
           for (uint32_t q = q0; q < q1; ++q) {
             const ms::Query &Q = R.queries[q - q0];
             uint64_t n = 0;
-            for (uint32_t k = 0; k < Q.nrows; ++k) n += row_total[Q.row_off + k];
+            for (uint32_t k = 0; k < Q.nrows; ++k) n += pb.row_total[Q.row_off + k];
             o->pair_off[q + 1] = o->pair_off[q] + n;
           }
-          groups.clear();
-          ms::plan_groups(row_total.data(), nrows, cap_pairs, R.tiles, groups);
           o->ms_scan += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
-          if (run) {
-            cs.timed(o->ms_scan, [&] { HIPCHK(hipMemcpyAsync(d_base.p, row_base.data(), (size_t)nrows * 8, hipMemcpyHostToDevice, cs.st)); });
-            for (const ms::Group &g : groups) {
-              const uint64_t n = g.npairs;
-              d_out.ensure(n * ms::PAIR_BYTES); h_out.ensure(n * ms::PAIR_BYTES);
-              uint32_t *di = d_out.as<uint32_t>();
-              const MsetOut mo = {d_base.as<uint64_t>(), d_total.as<uint32_t>(), g.base, n, di, di + n, di + 2 * n};
-              cs.timed(o->ms_fill, [&] {
-                launch_mset_tiles(cs.st, true, T, dq, dt, g.t_lo, g.t_hi, d_g.as<uint32_t>(), d_m.as<uint32_t>(), d_pk.as<ms::Entry>(), D, genome_threshold, g.row_lo, g.row_hi,
-                                  d_cnt.as<uint32_t>(), mo);
-                HIPCHK(hipGetLastError());
-              });
-              cs.timed(o->ms_download, [&] { HIPCHK(hipMemcpyAsync(h_out.p, d_out.p, n * ms::PAIR_BYTES, hipMemcpyDeviceToHost, cs.st)); });
-              const uint32_t *hi = h_out.as<uint32_t>();
-              o->pi.insert(o->pi.end(), hi, hi + n); o->pj.insert(o->pj.end(), hi + n, hi + 2 * n); o->count.insert(o->count.end(), hi + 2 * n, hi + 3 * n);
-              o->npairs += n; o->nbatches += 1;
-            }
-          }
         } else {
           for (uint32_t q = q0; q < q1; ++q) o->pair_off[q + 1] = o->pair_off[q];
         }

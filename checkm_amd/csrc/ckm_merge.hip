@@ -11,6 +11,7 @@
 #include <vector>
 #include "ckm_host.h"
 #include "merge_host.h"
+#include "pairs_host.h"
 
 namespace ckm {
 struct MergeBins {
@@ -65,8 +66,8 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
       const uint32_t nwords = mg::words_for(ngenes), ntj = mg::tiles_for(nbins);
       const size_t nb = nbins;
       cs.open(ctx->device);      // every phase below is waited for (cs.timed): the host needs its result before the next one
-      DevBuf d_bits, d_sum, d_n, d_stat, d_count, d_total, d_base, d_out;
-      PinnedBuf h_out;
+      DevBuf d_bits, d_sum, d_n, d_stat, d_count;
+      PairBatches pb;
       d_bits.ensure(nb * nwords * 8); d_sum.ensure(nb * 8); d_n.ensure(nb * 4); d_stat.ensure(nb * 16);
       cs.timed(o->ms_upload, [&] {
         HIPCHK(hipMemcpyAsync(d_bits.p, member_bits, nb * nwords * 8, hipMemcpyHostToDevice, cs.st));
@@ -76,56 +77,42 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
       const MergeBins B = {d_bits.as<uint64_t>(), d_sum.as<int64_t>(), d_n.as<int32_t>(), d_stat.as<double>(), d_stat.as<double>() + nb, nbins, nwords};
       cs.timed(o->ms_bins, [&] { launch_merge_bins(cs.st, B); HIPCHK(hipGetLastError()); });
       const uint32_t pass_rows = mg::count_pass_rows(nbins);
-      d_count.ensure((size_t)pass_rows * ntj * 4); d_total.ensure((size_t)pass_rows * 4); d_base.ensure((size_t)pass_rows * 8);
-      std::vector<uint32_t> row_total(pass_rows);
-      std::vector<uint64_t> row_base(pass_rows);
-      std::vector<mg::Group> groups;
+      d_count.ensure((size_t)pass_rows * ntj * 4);
       std::string lines;
+      // a batch on the host: columns first (8-byte values), then the two index columns
+      auto take = [&](const void *h_out, uint64_t n) {
+        const double *hc = static_cast<const double *>(h_out);
+        const uint32_t *hi = reinterpret_cast<const uint32_t *>(hc + mg::NCOL * n), *hj = hi + n;
+        if (o->kept) {
+          o->pi.insert(o->pi.end(), hi, hi + n); o->pj.insert(o->pj.end(), hj, hj + n);
+          for (int c = 0; c < mg::NCOL; ++c) o->col[c].insert(o->col[c].end(), hc + (size_t)c * n, hc + (size_t)(c + 1) * n);
+        }
+        if (fp) {
+          const auto w0 = std::chrono::steady_clock::now();
+          constexpr uint64_t STEP = 1 << 16;                 // the text of a batch is several times its columns: formatted and written in pieces
+          for (uint64_t k = 0; k < n; k += STEP) {
+            const uint64_t m = std::min<uint64_t>(STEP, n - k);
+            lines.clear();
+            mg::format_lines(lines, bin_ids, hi + k, hj + k, hc + k, n, m);
+            if (fwrite(lines.data(), 1, lines.size(), fp.get()) != lines.size()) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
+          }
+          o->ms_write += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+        }
+        o->npairs += n; o->nbatches += 1;
+      };
       for (uint32_t r0 = 0; r0 < nbins; r0 += pass_rows) {
         const uint32_t r1 = std::min<uint64_t>(nbins, (uint64_t)r0 + pass_rows), nr = r1 - r0;
         MergeOut none = {nullptr, 0, 0, nullptr, nullptr, nullptr};
         cs.timed(o->ms_count, [&] { launch_merge_tiles(cs.st, false, B, T, r0, r1, r0, d_count.as<uint32_t>(), none); HIPCHK(hipGetLastError()); });
-        cs.timed(o->ms_scan, [&] {
-          launch_merge_scan(cs.st, r0, nr, ntj, d_count.as<uint32_t>(), d_total.as<uint32_t>());
-          HIPCHK(hipGetLastError());
-          HIPCHK(hipMemcpyAsync(row_total.data(), d_total.p, (size_t)nr * 4, hipMemcpyDeviceToHost, cs.st));
-        });
-        const auto s0 = std::chrono::steady_clock::now();
-        uint64_t run = 0;
-        for (uint32_t k = 0; k < nr; ++k) { row_base[k] = run; run += row_total[k]; }
-        groups.clear();
-        mg::plan_groups(row_total.data(), r0, r1, cap_pairs, groups);
-        o->ms_scan += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
-        if (!run) continue;
-        cs.timed(o->ms_scan, [&] { HIPCHK(hipMemcpyAsync(d_base.p, row_base.data(), (size_t)nr * 8, hipMemcpyHostToDevice, cs.st)); });
-        for (const mg::Group &g : groups) {
-          const uint64_t n = g.npairs;
-          d_out.ensure(n * mg::PAIR_BYTES); h_out.ensure(n * mg::PAIR_BYTES);
-          // columns first (8-byte values), then the two index columns
-          double *dc = d_out.as<double>();
-          uint32_t *di = reinterpret_cast<uint32_t *>(dc + mg::NCOL * n);
-          const MergeOut mo = {d_base.as<uint64_t>(), g.base, n, di, di + n, dc};
-          cs.timed(o->ms_fill, [&] { launch_merge_tiles(cs.st, true, B, T, g.row_lo, g.row_hi, r0, d_count.as<uint32_t>(), mo); HIPCHK(hipGetLastError()); });
-          cs.timed(o->ms_download, [&] { HIPCHK(hipMemcpyAsync(h_out.p, d_out.p, n * mg::PAIR_BYTES, hipMemcpyDeviceToHost, cs.st)); });
-          const double *hc = h_out.as<double>();
-          const uint32_t *hi = reinterpret_cast<const uint32_t *>(hc + mg::NCOL * n), *hj = hi + n;
-          if (o->kept) {
-            o->pi.insert(o->pi.end(), hi, hi + n); o->pj.insert(o->pj.end(), hj, hj + n);
-            for (int c = 0; c < mg::NCOL; ++c) o->col[c].insert(o->col[c].end(), hc + (size_t)c * n, hc + (size_t)(c + 1) * n);
-          }
-          if (fp) {
-            const auto w0 = std::chrono::steady_clock::now();
-            constexpr uint64_t STEP = 1 << 16;                 // the text of a batch is several times its columns: formatted and written in pieces
-            for (uint64_t k = 0; k < n; k += STEP) {
-              const uint64_t m = std::min<uint64_t>(STEP, n - k);
-              lines.clear();
-              mg::format_lines(lines, bin_ids, hi + k, hj + k, hc + k, n, m);
-              if (fwrite(lines.data(), 1, lines.size(), fp.get()) != lines.size()) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
-            }
-            o->ms_write += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-          }
-          o->npairs += n; o->nbatches += 1;
-        }
+        pb.run(cs, r0, nr, cap_pairs, mg::PAIR_BYTES, o->ms_scan, o->ms_fill, o->ms_download,
+               [&](uint32_t *d_total) { launch_merge_scan(cs.st, r0, nr, ntj, d_count.as<uint32_t>(), d_total); },
+               [&](const pc::Group &g, void *d_out, uint64_t n) {
+                 double *dc = static_cast<double *>(d_out);
+                 uint32_t *di = reinterpret_cast<uint32_t *>(dc + mg::NCOL * n);
+                 const MergeOut mo = {pb.d_base.as<uint64_t>(), g.base, n, di, di + n, dc};
+                 launch_merge_tiles(cs.st, true, B, T, g.row_lo, g.row_hi, r0, d_count.as<uint32_t>(), mo);
+               },
+               take);
       }
     }
     if (fp && fclose(fp.release()) != 0) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);

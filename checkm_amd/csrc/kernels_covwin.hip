@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "covwin_dev.h"
+#include "pairs_wave.h"
 
 namespace ckm {
 using namespace cw;
@@ -92,11 +93,7 @@ __global__ __launch_bounds__(256) void covwin_kernel(const uint8_t *__restrict__
 // inclusive scan of v over the workgroup's SCAN_THREADS threads; *total = the workgroup's sum.  lds: SCAN_THREADS / WAVE values.
 __device__ __forceinline__ long long block_scan(long long v, long long *lds, long long *total) {
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-#pragma unroll
-  for (int d = 1; d < WAVE; d <<= 1) {
-    const long long up = __shfl_up(v, d, WAVE);
-    if (lane >= d) v += up;
-  }
+  v = wave_inclusive(v, lane);
   __syncthreads();                                             // (the previous use of lds has been read)
   if (lane == WAVE - 1) lds[wave] = v;
   __syncthreads();

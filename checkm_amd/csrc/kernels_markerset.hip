@@ -13,15 +13,13 @@
 //                        Per GCHUNK genomes the entries of the 64 row markers and the 64 column markers, and the genome indices, are
 //                        staged in LDS (the row side is read by a whole wavefront at one address: a broadcast).  The single-copy case is a
 //                        subtraction and a compare; more copies walk the table's own list.  Then a row at a time: the reference's test, a
-//                        64-bit ballot.
-//                          count pass  lane 0 stores the ballot's popcount at [row][tile column]
-//                          fill pass   tiles without a reported pair exit at once; else the same predicate again; a reported pair goes to
-//                                      row_base[row] + tile_off[row][tile column] + (reported lanes below this one): the output is in
-//                                      (query, i, j) order and no atomic decides a position.
-//   mset_scan_kernel     a wavefront per row of the round: exclusive prefix of the row's tile counts in place, the row's total out.
+//                        64-bit ballot, and the count or the fill step of pairs_wave.h: the output is in (query, i, j) order and no atomic
+//                        decides a position.  In the fill pass a tile without a reported pair exits at once.
+//   mset_scan_kernel     a wavefront per row of the round: pc::row_scan over the row's tile counts, the row's total out.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "markerset_dev.h"
+#include "pairs_wave.h"
 
 namespace ckm {
 using namespace ms;
@@ -133,9 +131,9 @@ __global__ __launch_bounds__(THREADS) void mset_tile_kernel(MsetTableDev T, cons
     const uint64_t ballot = __ballot(keep);
     const uint64_t at = Q.cnt_off + (uint64_t)i * ntj + tile.tj;
     if (!FILL) {
-      if (lane == 0) tile_count[at] = (uint32_t)__popcll(ballot);
+      pc::count_store(ballot, lane, tile_count, at);
     } else if (keep) {
-      const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+      const int below = pc::lanes_below(ballot);
       const uint64_t slot = pair_slot(out.row_base[row], tile_count[at], below, out.batch_base);
       if (slot < out.cap) { out.pi[slot] = i; out.pj[slot] = j; out.count[slot] = cnt[r]; }
     }
@@ -149,20 +147,8 @@ __global__ __launch_bounds__(THREADS) void mset_scan_kernel(const Query *__restr
   if (k >= nrows) return;
   const Query Q = queries[find_query(nq, k, [&](uint32_t q) { return (uint64_t)queries[q].row_off; })];
   const uint32_t i = k - Q.row_off, ntj = tiles_for(Q.nm);
-  uint32_t *row = tile_count + Q.cnt_off + (uint64_t)i * ntj;
-  uint32_t carry = 0;
-  for (uint32_t base = i / (uint32_t)TILE; base < ntj; base += WAVE) {
-    const uint32_t t = base + (uint32_t)lane;
-    const uint32_t v = t < ntj ? row[t] : 0u;
-    uint32_t incl = v;
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, WAVE);
-      if (lane >= d) incl += up;
-    }
-    if (t < ntj) row[t] = carry + incl - v;
-    carry += __shfl(incl, WAVE - 1, WAVE);
-  }
-  if (lane == 0) row_total[k] = carry;
+  const uint32_t total = pc::row_scan(tile_count + Q.cnt_off + (uint64_t)i * ntj, 1u, i / (uint32_t)TILE, ntj, lane);
+  if (lane == 0) row_total[k] = total;
 }
 
 // queries [q0, q0 + nq) of the call; flag and counts start at q0

@@ -9,17 +9,15 @@
 //   merge_tile_kernel   a block of four wavefronts per tile, a lane per column j.  The rows of both sides are staged in LDS sixteen words
 //                       at a time (the J side transposed: lane j reads word k at [k][j], no bank conflict; the I side is read by a whole
 //                       wavefront at one address: a broadcast) and reused by the sixteen rows a wavefront walks; the union counts of
-//                       those sixteen rows live in registers.  Then a row at a time: the two tests of the reference, a 64-bit ballot.
-//                         count pass  lane 0 stores the ballot's popcount at [row][tile]
-//                         fill pass   the same predicate again; a reported pair goes to
-//                                     row_base[row] + tile_off[row][tile] + (reported lanes below this one), so the output is in
-//                                     (i, j) order and no atomic decides a position.
-//   merge_scan_kernel   a wavefront per row: exclusive prefix of the row's tile counts in place (tiles left of the diagonal count as
-//                       nothing and are never read), the row's total out.  The prefix over the rows is the host's (it needs the totals
-//                       to cut the output into batches).
+//                       those sixteen rows live in registers.  Then a row at a time: the two tests of the reference, a 64-bit ballot,
+//                       and the count or the fill step of pairs_wave.h (count_store; lanes_below and pair_slot): the output is in (i, j) order and no atomic decides a position.
+//   merge_scan_kernel   a wavefront per row: pc::row_scan over the row's tile counts (tiles left of the diagonal count as nothing and
+//                       are never read), the row's total out.  The prefix over the rows is the host's (it needs the totals to cut the
+//                       output into batches).
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "merge_dev.h"
+#include "pairs_wave.h"
 
 namespace ckm {
 using namespace mg;
@@ -90,9 +88,9 @@ __global__ __launch_bounds__(256) void merge_tile_kernel(MergeBins B, Thresholds
     const uint64_t ballot = __ballot(keep);
     const uint64_t at = (uint64_t)(i - count_row0) * ntiles_j + tj;
     if (!FILL) {
-      if (lane == 0) tile_count[at] = (uint32_t)__popcll(ballot);
+      pc::count_store(ballot, lane, tile_count, at);
     } else if (keep) {
-      const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+      const int below = pc::lanes_below(ballot);
       const uint64_t slot = pair_slot(out.row_base[i - count_row0], tile_count[at], below, out.batch_base);
       if (slot < out.cap) {
         out.pi[slot] = i; out.pj[slot] = j;
@@ -107,20 +105,8 @@ __global__ __launch_bounds__(256) void merge_scan_kernel(uint32_t row0, uint32_t
   const int lane = threadIdx.x & (WAVE - 1);
   const uint32_t k = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (k >= nrows) return;
-  uint32_t *row = tile_count + (uint64_t)k * ntiles_j;
-  uint32_t carry = 0;
-  for (uint32_t base = (row0 + k) / (uint32_t)TILE_I; base < ntiles_j; base += WAVE) {
-    const uint32_t t = base + (uint32_t)lane;
-    const uint32_t v = t < ntiles_j ? row[t] : 0u;
-    uint32_t incl = v;
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, WAVE);
-      if (lane >= d) incl += up;
-    }
-    if (t < ntiles_j) row[t] = carry + incl - v;
-    carry += __shfl(incl, WAVE - 1, WAVE);
-  }
-  if (lane == 0) row_total[k] = carry;
+  const uint32_t total = pc::row_scan(tile_count + (uint64_t)k * ntiles_j, 1u, (row0 + k) / (uint32_t)TILE_I, ntiles_j, lane);
+  if (lane == 0) row_total[k] = total;
 }
 
 void launch_merge_bins(hipStream_t st, const MergeBins &B) {

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "nucstats_dev.h"
+#include "pairs_wave.h"
 #include "tetra_wave.h"
 
 namespace ckm {
@@ -41,15 +42,6 @@ __device__ __forceinline__ void load_lane(const uint8_t *text, const Tile &T, ui
   b[0] = (uint8_t)prev;
 #pragma unroll
   for (int k = 0; k < 28; ++k) b[1 + k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x, int lane) {
-#pragma unroll
-  for (int s = 1; s < WAVE; s <<= 1) {
-    const uint32_t y = __shfl_up(x, s);
-    if (lane >= s) x += y;
-  }
-  return x;
 }
 
 __global__ __launch_bounds__(256) void nucstats_count_kernel(const uint8_t *__restrict__ text, const Tile *__restrict__ tiles, uint32_t ntiles,
@@ -109,7 +101,7 @@ __global__ __launch_bounds__(256) void nucstats_fill_kernel(const uint8_t *__res
     Lane o;
     lane_step(b, nvalid, in_seq, has_prev, o);
     const uint32_t nn = (uint32_t)__builtin_popcount(o.nonn_mask), ne = (uint32_t)__builtin_popcount(o.ev_mask);
-    const uint32_t inc = wave_incl_scan(nn | (ne << 16), lane);     // both at most 1024 per step: two 16-bit halves do not carry
+    const uint32_t inc = wave_inclusive(nn | (ne << 16), lane);     // both at most 1024 per step: two 16-bit halves do not carry
     const uint32_t exc = inc - (nn | (ne << 16));
     uint64_t my_slot = slot + (exc >> 16);
     const uint64_t my_before = before + (exc & 0xFFFFu);

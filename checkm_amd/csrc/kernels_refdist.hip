@@ -8,13 +8,14 @@
 //                          one aligned 128-bit load per lane, the bytes outside the block masked, the three bytes a 4-mer needs behind
 //                          a chunk taken from the next lane's word.  A 4-mer belongs to the block where it STARTS.  GC / CD: two
 //                          counters summed over the wave; TD: a histogram of the wave's own in LDS.  The block's row is a plain store.
-//   refdist_scan_kernel    a wavefront per column: exclusive scan over the blocks with a carry across steps of 64 (the shape of
-//                          merge_scan_kernel); row nblocks receives the totals of the scaffold.
+//   refdist_scan_kernel    a wavefront per column: pc::row_scan (pairs_wave.h) down the column, an exclusive scan over the blocks;
+//                          row nblocks receives the totals of the scaffold.
 //   refdist_window_kernel  a wavefront per window: P[b1] - P[b0] over its whole blocks plus its edges (fewer than two blocks of text),
 //                          read as the block kernel reads a block.  GC / CD: two uint32 per window; TD: the window's 136 counts.
 // No global atomics anywhere: every row has one writer.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "pairs_wave.h"
 #include "refdist_dev.h"
 #include "tetra_wave.h"
 
@@ -48,19 +49,8 @@ __global__ __launch_bounds__(256) void refdist_scan_kernel(uint32_t *__restrict_
   const int lane = threadIdx.x & (WAVE - 1);
   const uint32_t col = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (col >= ncol) return;
-  uint32_t carry = 0;                                       // at most the scaffold's length, below 2^31
-  for (uint32_t base = 0; base < nblocks; base += WAVE) {
-    const uint32_t t = base + (uint32_t)lane;
-    const uint32_t v = t < nblocks ? rows[(uint64_t)t * ncol + col] : 0u;
-    uint32_t incl = v;
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t up = __shfl_up(incl, d, WAVE);
-      if (lane >= d) incl += up;
-    }
-    if (t < nblocks) rows[(uint64_t)t * ncol + col] = carry + incl - v;
-    carry += __shfl(incl, WAVE - 1, WAVE);
-  }
-  if (lane == 0) rows[(uint64_t)nblocks * ncol + col] = carry;
+  const uint32_t total = pc::row_scan(rows + col, ncol, 0u, nblocks, lane);      // at most the scaffold's length, below 2^31
+  if (lane == 0) rows[(uint64_t)nblocks * ncol + col] = total;
 }
 
 // windows win0 .. win0 + nwin - 1 of the call; tet holds the rows of this launch only (row 0 = window win0)

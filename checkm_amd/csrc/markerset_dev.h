@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "pairs_dev.h"
 #include "wave_const.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -102,16 +103,10 @@ MS_HD bool reported(uint32_t count, uint32_t ngenomes, double genome_threshold) 
   return (double)count / (double)ngenomes > genome_threshold;
 }
 
-// Where the fill pass puts a reported pair (merge_dev.h: pair_slot)
-MS_HD uint64_t pair_slot(uint64_t row_base, uint32_t tile_off, int below, uint64_t batch_base) {
-  return row_base + tile_off + (uint64_t)below - batch_base;
-}
-
-// After the scan a row's tile counts are offsets: what row i reports in tile column tj is the next column's offset (behind the last
-// column: the row's total) minus its own.  The fill pass skips a tile none of whose rows reports anything.
-MS_HD uint32_t tile_pairs(const uint32_t *row_offsets, uint32_t tj, uint32_t ntj, uint32_t row_total) {
-  return (tj + 1 < ntj ? row_offsets[tj + 1] : row_total) - row_offsets[tj];
-}
+// Where the fill pass puts a reported pair, and what a row reports in a tile column after the scan (the fill pass skips a tile none of
+// whose rows reports anything): pairs_dev.h
+using pc::pair_slot;
+using pc::tile_pairs;
 
 // the last query q of [0, n) with key(q) <= x; key never falls and key(0) <= x.  Queries without entries repeat their neighbour's key and
 // are never the answer for an x that belongs to somebody.
@@ -227,31 +222,27 @@ inline void build_round(const uint64_t *qg_off, const uint64_t *qm_off, uint32_t
   }
 }
 
-inline uint64_t budget_pairs(uint64_t budget_bytes) { return std::max<uint64_t>(1, budget_bytes / PAIR_BYTES); }
+inline uint64_t budget_pairs(uint64_t budget_bytes) { return pc::budget_pairs(budget_bytes, PAIR_BYTES); }
 
-// An output batch: rows [row_lo, row_hi) of the round, whose reported pairs are [base, base + npairs) of the round, and the tiles
-// [t_lo, t_hi) of the round's list that hold those rows.
-struct Group { uint32_t row_lo, row_hi; uint64_t base, npairs; uint32_t t_lo, t_hi; };
+// The tiles [t_lo, t_hi) of the round's list that hold the rows of an output batch (pairs_dev.h; the rows of a round are the rows of its
+// count pass).  row0 never falls along the list: the tiles with a row in [row_lo, row_hi) are one stretch of it.
+struct TileRange { uint32_t t_lo, t_hi; };
+inline TileRange tile_range(const pc::Group &g, const std::vector<Tile> &tiles) {
+  const auto lo = std::partition_point(tiles.begin(), tiles.end(), [&](const Tile &t) { return (uint64_t)t.row0 + TILE <= g.row_lo; });
+  const auto hi = std::partition_point(tiles.begin(), tiles.end(), [&](const Tile &t) { return t.row0 < g.row_hi; });
+  return TileRange{(uint32_t)(lo - tiles.begin()), (uint32_t)(hi - tiles.begin())};
+}
 
-// Whole rows, in order, as many as fit `cap` pairs; a row that reports more than `cap` by itself is a batch of its own.  Rows without a
-// reported pair never open a batch.
+// The output batches of a round, each with its tiles: what the fill launches of a round walk, for the host executor of the CPU tests
+struct Group : pc::Group { uint32_t t_lo, t_hi; };
 inline void plan_groups(const uint32_t *row_total, uint32_t nrows, uint64_t cap, const std::vector<Tile> &tiles, std::vector<Group> &out) {
-  uint64_t base = 0;
-  Group g = {0, 0, 0, 0, 0, 0};
-  auto close = [&](uint32_t row_hi) {
-    g.row_hi = row_hi;
-    // row0 never falls along the list: the tiles with a row in [row_lo, row_hi) are one stretch of it
-    g.t_lo = (uint32_t)(std::partition_point(tiles.begin(), tiles.end(), [&](const Tile &t) { return (uint64_t)t.row0 + TILE <= g.row_lo; }) - tiles.begin());
-    g.t_hi = (uint32_t)(std::partition_point(tiles.begin(), tiles.end(), [&](const Tile &t) { return t.row0 < g.row_hi; }) - tiles.begin());
-    out.push_back(g);
-  };
-  for (uint32_t r = 0; r < nrows; ++r) {
-    const uint64_t n = row_total[r];
-    if (g.npairs && g.npairs + n > cap) { close(r); g = Group{r, r, base, 0, 0, 0}; }
-    if (!g.npairs) { g.row_lo = r; g.base = base; }
-    g.npairs += n; base += n;
+  std::vector<pc::Group> rows;
+  pc::plan_groups(row_total, 0, nrows, cap, rows);
+  for (const pc::Group &g : rows) {
+    const TileRange t = tile_range(g, tiles);
+    Group G; static_cast<pc::Group &>(G) = g; G.t_lo = t.t_lo; G.t_hi = t.t_hi;
+    out.push_back(G);
   }
-  if (g.npairs) close(nrows);
 }
 
 }  // namespace ms

@@ -15,6 +15,7 @@
 // 2^46), the division second.  The library and the host executor are built with -ffp-contract=off and without fast-math.
 #pragma once
 #include <cstdint>
+#include "pairs_dev.h"
 #include "wave_const.h"
 
 #if defined(__HIP__)
@@ -39,6 +40,8 @@ struct Thresholds { double min_delta_comp, max_delta_cont, min_merged_comp, max_
 
 // the per-bin operands of a pair
 struct BinSide { int64_t hit_sum; int32_t n_markers; double comp, cont; };
+
+using pc::pair_slot;                             // where the fill pass puts a reported pair
 
 struct PairCols { double v[NCOL]; };             // compI, contI, compJ, contJ, deltaComp, deltaCont, delta, compM, contM
 
@@ -72,12 +75,6 @@ MG_HD bool pair_eval(int32_t u, const BinSide &I, const BinSide &J, const Thresh
   out.v[0] = I.comp; out.v[1] = I.cont; out.v[2] = J.comp; out.v[3] = J.cont;
   out.v[4] = d_comp; out.v[5] = d_cont; out.v[6] = delta; out.v[7] = comp_m; out.v[8] = cont_m;
   return d_comp >= t.min_delta_comp && d_cont < t.max_delta_cont;
-}
-
-// Where the fill pass puts a reported pair: row_base[i] = pairs reported by the rows before i, tile_off = pairs of row i in the
-// tiles left of this one, below = reported pairs of this row and tile in lower lanes; minus the first pair of the output batch.
-MG_HD uint64_t pair_slot(uint64_t row_base, uint32_t tile_off, int below, uint64_t batch_base) {
-  return row_base + tile_off + (uint64_t)below - batch_base;
 }
 
 }  // namespace mg

@@ -1,6 +1,6 @@
-// merge_host.h -- the host side of `checkm merge` that needs no device: argument checks, the split of the rows into output batches and the
-// lines of merger.tsv (checkm/merger.py:101-106).  Plain C++, used by ckm_merge.hip, by the host executor of the CPU tests
-// (tests/emu/merge_emu.cpp) and by the sanitizer harness (tests/native/merge_host_check.cpp).
+// merge_host.h -- the host side of `checkm merge` that needs no device: argument checks, the rows of a count pass and the lines of
+// merger.tsv (checkm/merger.py:101-106); the split of a pass's rows into output batches is pairs_dev.h's.  Plain C++, used by ckm_merge.hip,
+// by the host executor of the CPU tests (tests/emu/merge_emu.cpp) and by the sanitizer harness (tests/native/merge_host_check.cpp).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -35,30 +35,16 @@ inline std::string check_args(uint32_t nbins, uint32_t ngenes, const uint64_t *b
   return std::string();
 }
 
-inline uint64_t budget_pairs(uint64_t budget_bytes) { return std::max<uint64_t>(1, budget_bytes / PAIR_BYTES); }
+// pairs an output batch may hold; its rows are pairs_dev.h's Group and plan_groups
+inline uint64_t budget_pairs(uint64_t budget_bytes) { return pc::budget_pairs(budget_bytes, PAIR_BYTES); }
+using pc::Group;
+using pc::plan_groups;
 
 // rows of one count pass: whole tiles, the counts within COUNT_BYTES
 inline uint32_t count_pass_rows(uint32_t nbins) {
   const uint64_t per_row = (uint64_t)tiles_for(nbins) * sizeof(uint32_t);
   const uint64_t rows = std::max<uint64_t>(TILE_I, COUNT_BYTES / std::max<uint64_t>(1, per_row) / TILE_I * TILE_I);
   return (uint32_t)std::min<uint64_t>(rows, (uint64_t)tiles_for(nbins) * TILE_I);
-}
-
-// An output batch: rows [row_lo, row_hi) whose reported pairs are [base, base + npairs) of the count pass they belong to.
-struct Group { uint32_t row_lo, row_hi; uint64_t base, npairs; };
-
-// Whole rows, in order, as many as fit `cap` pairs; a row that reports more than `cap` by itself is a batch of its own.  Rows without
-// a reported pair never open a batch.  row_total[k] belongs to row r0 + k.
-inline void plan_groups(const uint32_t *row_total, uint32_t r0, uint32_t r1, uint64_t cap, std::vector<Group> &out) {
-  uint64_t base = 0;
-  Group g = {r0, r0, 0, 0};
-  for (uint32_t r = r0; r < r1; ++r) {
-    const uint64_t n = row_total[r - r0];
-    if (g.npairs && g.npairs + n > cap) { g.row_hi = r; out.push_back(g); g = Group{r, r, base, 0}; }
-    if (!g.npairs) { g.row_lo = r; g.base = base; }
-    g.npairs += n; base += n;
-  }
-  if (g.npairs) { g.row_hi = r1; out.push_back(g); }
 }
 
 // '%s\t%s' + 9 x '\t%.2f' + '\n' for n pairs; cols[c * stride + k] is column c of pair k.  glibc's %.2f rounds the exact binary value

@@ -15,7 +15,7 @@ _lib = None
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, "markerset_emu.cpp"), os.path.join(_CSRC, "markerset_dev.h")]
+    srcs = [os.path.join(_HERE, "markerset_emu.cpp"), os.path.join(_CSRC, "markerset_dev.h"), os.path.join(_CSRC, "pairs_dev.h")]
     if force or not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-ffp-contract=off", "-o", _LIB,
                                os.path.join(_HERE, "markerset_emu.cpp")])

@@ -101,13 +101,8 @@ void scan(const ms::Round &R, std::vector<uint32_t> &tile_count, std::vector<uin
   for (uint32_t k = 0; k < R.rows; ++k) {
     const ms::Query Q = R.queries[ms::find_query(nq, k, [&](uint32_t q) { return (uint64_t)R.queries[q].row_off; })];
     const uint32_t i = k - Q.row_off, ntj = ms::tiles_for(Q.nm);
-    uint32_t carry = 0;
-    for (uint32_t t = i / ms::TILE; t < ntj; ++t) {
-      uint32_t &v = tile_count.at(Q.cnt_off + (uint64_t)i * ntj + t);
-      const uint32_t x = v;
-      v = carry; carry += x;
-    }
-    row_total.at(k) = carry;
+    (void)tile_count.at(Q.cnt_off + (uint64_t)i * ntj + ntj - 1);                          // the whole row lies in the buffer
+    row_total.at(k) = pc::row_scan_host(&tile_count.at(Q.cnt_off + (uint64_t)i * ntj), 1, i / ms::TILE, ntj);
   }
 }
 }  // namespace
@@ -178,8 +173,7 @@ extern "C" int emu_mset_colocated(uint32_t G, uint32_t C, const uint8_t *cls, co
       tile_count.assign(R.counts, 0xDEADBEEFu); row_total.assign(R.rows, 0xDEADBEEFu); row_base.assign(R.rows, 0);
       for (const ms::Tile &t : R.tiles) tile_block(false, T, R, t, qg, qm, pk, D, thr, 0, R.rows, tile_count, row_base, row_total, 0, pi, pj, pc);
       scan(R, tile_count, row_total);
-      uint64_t run = 0;
-      for (uint32_t k = 0; k < R.rows; ++k) { row_base[k] = run; run += row_total[k]; }
+      const uint64_t run = pc::row_prefix(row_total.data(), R.rows, row_base.data());
       for (uint32_t q = q0; q < q1; ++q) {
         const ms::Query &Q = R.queries[q - q0];
         uint64_t n = 0;

@@ -15,7 +15,7 @@ COLUMNS = ("comp_i", "cont_i", "comp_j", "cont_j", "delta_comp", "delta_cont", "
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, "merge_emu.cpp"), os.path.join(_CSRC, "merge_dev.h"), os.path.join(_CSRC, "merge_host.h")]
+    srcs = [os.path.join(_HERE, "merge_emu.cpp"), os.path.join(_CSRC, "merge_dev.h"), os.path.join(_CSRC, "merge_host.h"), os.path.join(_CSRC, "pairs_dev.h")]
     if force or not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas",
                                "-o", _LIB, os.path.join(_HERE, "merge_emu.cpp")])

@@ -1,4 +1,4 @@
-// merge_emu.cpp -- TEST INFRASTRUCTURE: the all-pairs comparison of `checkm merge` (checkm_amd/csrc/merge_dev.h, merge_host.h) compiled by
+// merge_emu.cpp -- TEST INFRASTRUCTURE: the all-pairs comparison of `checkm merge` (checkm_amd/csrc/merge_dev.h, merge_host.h, pairs_dev.h) compiled by
 // g++ against a HOST executor, so that the CPU test suite runs the arithmetic, the placement of the reported pairs and the split into
 // output batches of the library.  The kernels of kernels_merge.hip are restated as loops over their tiles, wavefronts and lanes: a
 // ballot is a 64-bit word built lane by lane, the lanes below are its low bits.  Built with -ffp-contract=off like the library.
@@ -9,6 +9,7 @@
 #include "../../checkm_amd/csrc/merge_host.h"
 
 using namespace ckm::mg;
+namespace pc = ckm::pc;
 
 namespace {
 
@@ -89,13 +90,8 @@ extern "C" int64_t emu_merge(uint32_t nbins, uint32_t ngenes, const uint64_t *bi
     const Out none = {nullptr, 0, 0, nullptr, nullptr, nullptr};
     for (uint32_t ti = r0 / TILE_I; ti < (r1 - 1) / TILE_I + 1; ++ti)
       for (uint32_t tj = 0; tj < ntj; ++tj) tile(false, B, T, r0, r1, ti, tj, ntj, r0, tile_count, none);
-    for (uint32_t k = 0; k < nr; ++k) {                                        // merge_scan_kernel
-      uint32_t carry = 0;
-      for (uint32_t t = (r0 + k) / TILE_I; t < ntj; ++t) { const uint32_t v = tile_count[(size_t)k * ntj + t]; tile_count[(size_t)k * ntj + t] = carry; carry += v; }
-      row_total[k] = carry;
-    }
-    uint64_t run = 0;
-    for (uint32_t k = 0; k < nr; ++k) { row_base[k] = run; run += row_total[k]; }
+    for (uint32_t k = 0; k < nr; ++k) row_total[k] = pc::row_scan_host(&tile_count[(size_t)k * ntj], 1, (r0 + k) / TILE_I, ntj);      // merge_scan_kernel
+    const uint64_t run = pc::row_prefix(row_total.data(), nr, row_base.data());
     groups.clear();
     plan_groups(row_total.data(), r0, r1, cap_pairs, groups);
     uint64_t seen = 0;

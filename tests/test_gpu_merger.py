@@ -11,6 +11,7 @@ import pytest
 
 from checkm_amd import _lib
 from tests import merger_common as mc
+from tests.emu import merge as emu
 
 pytestmark = pytest.mark.gpu
 
@@ -139,6 +140,40 @@ def test_output_batches_do_not_change_the_file(gpu_ctx, tmp_path):
     assert head == mc.write_lines(ids, i, j, cols).splitlines()[:3]
     i, j, cols = mc.restate(member[-3:], hit_sum[-3:], n_markers[-3:], LOOSE)
     assert tail == mc.write_lines(ids[-3:], i, j, cols).splitlines()[-2:]
+
+
+def test_small_shapes_and_batches_equal_the_host_executor(gpu_ctx):
+    """The placement edges of the fill pass: fewer bins than a tile, exactly one, one more, three tile columns with a ragged last one;
+    bit rows of one word, of one word and a bit, past one staged chunk of sixteen.  Every pair reported, and thresholds under which rows
+    without a reported pair exist.  Output budgets of the default, of one 80-byte pair (every reporting row is a batch of its own) and of a
+    hundred pairs, against the host executor of the kernels' source with the same batch caps: the pairs, their order, the nine columns and
+    the number of batches are equal with ==."""
+    some = [0.0, 25.0, 55.0, 35.0]
+    for nbins in (2, 64, 65, 129, 200):
+        for ngenes in (1, 64, 65, 1030):
+            member, hit_sum, n_markers = mc.synthetic(nbins, ngenes, seed=11, lo=0.36, hi=0.99, dup=0.01)
+            bits = mc.pack(member)
+            for thr in (LOOSE, some):
+                seen = {}
+                for budget, cap in ((0, 0), (80, 1), (8000, 100)):
+                    want = emu.merge_pairs(bits, hit_sum, n_markers, ngenes, thr, cap_pairs=cap)
+                    res = _lib.merge_pairs(gpu_ctx, bits, hit_sum, n_markers, ngenes, thr, budget_bytes=budget)
+                    where = (nbins, ngenes, thr, budget)
+                    assert res["npairs"] == want["npairs"] and res["nbatches"] == want["nbatches"], where
+                    assert (res["i"] == want["i"]).all() and (res["j"] == want["j"]).all(), where
+                    for f in mc.COLUMNS:
+                        assert (res[f] == want[f]).all(), (where, f)
+                    seen[budget] = (want["npairs"], want["nbatches"])
+                # the inputs are the ones the edges need: these figures are the host executor's
+                if thr is LOOSE:
+                    assert seen[0] == (nbins * (nbins - 1) // 2, 1)
+                    if nbins == 65:
+                        assert seen[80] == (2080, 64) and seen[8000] == (2080, 29)
+                    if nbins == 200:
+                        assert seen[80] == (19900, 199) and seen[8000] == (19900, 164)
+                elif nbins >= 64:
+                    assert 263 <= seen[0][0] <= 6643 and 27 <= seen[80][1] <= 197 and 3 <= seen[8000][1] <= 80, (where, seen)
+                    assert seen[80][1] < nbins - 1, (where, seen)          # rows without a reported pair exist: they open no batch
 
 
 def test_merge_pairs_refuses_bad_arguments_on_the_device(gpu_ctx):
