@@ -193,6 +193,16 @@ class MsetColumns(C.Structure):
                [(f, C.c_double) for f in ("ms_upload", "ms_markers", "ms_pack", "ms_count", "ms_scan", "ms_fill", "ms_download", "ms_total")]
 
 
+class SimArgs(C.Structure):
+    _fields_ = [("nmarkers", C.c_uint32), ("key_off", C.c_void_p), ("key", C.c_void_p), ("nkeys", C.c_uint64),
+                ("nsets", C.c_uint32), ("ms_off", C.c_void_p), ("cs_off", C.c_void_p), ("ncs", C.c_uint64), ("cs_marker", C.c_void_p), ("nmembers", C.c_uint64),
+                ("nreplicates", C.c_uint32), ("rs_off", C.c_void_p), ("starts", C.c_void_p), ("nstarts", C.c_uint64), ("contig_len", C.c_void_p)]
+
+
+class SimInfo(C.Structure):
+    _fields_ = [("nrounds", C.c_uint64)] + [(f, C.c_double) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -231,6 +241,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_fasta_ids_read", "ckm_fasta_ids_view_get", "ckm_fasta_ids_free", "ckm_unbinned_select", "ckm_unbinned_count", "ckm_unbinned_write",
            "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
+           "ckm_sim_check", "ckm_sim_run",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -363,6 +374,8 @@ def load():
     L.ckm_mset_columns_get.argtypes = [C.c_void_p, C.POINTER(MsetColumns)]
     L.ckm_mset_result_free.argtypes = [C.c_void_p]
     L.ckm_mset_result_free.restype = None
+    L.ckm_sim_check.argtypes = [C.POINTER(SimArgs)]
+    L.ckm_sim_run.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_uint64, C.c_void_p, C.POINTER(SimInfo)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1499,3 +1512,43 @@ def mset_colocated(ctx, table, genome_lists, marker_lists, dist_threshold=5000, 
     finally:
         load().ckm_mset_result_free(h)
     return out
+
+
+class SimTables(object):
+    """The arrays of one simulation call as ckm_sim_check / ckm_sim_run take them (include/checkm_hip.h): key_off / key for the distinct
+    markers, ms_off / cs_off / cs_marker for the marker sets, rs_off / starts / contig_len for the replicates.  Keys, starts and contig
+    lengths are int64 here; the library checks them down to int32."""
+
+    def __init__(self, key_off, key, ms_off, cs_off, cs_marker, rs_off, starts, contig_len):
+        u64 = lambda x: np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+        i64 = lambda x: np.ascontiguousarray(x, dtype=np.int64).reshape(-1)
+        self.key_off, self.key, self.ms_off, self.cs_off, self.rs_off = u64(key_off), i64(key), u64(ms_off), u64(cs_off), u64(rs_off)
+        self.cs_marker = np.ascontiguousarray(cs_marker, dtype=np.uint32).reshape(-1)
+        self.starts, self.contig_len = i64(starts), i64(contig_len)
+        if not (self.key_off.size and self.ms_off.size and self.cs_off.size and self.rs_off.size):
+            raise ValueError("an offset table holds at least its leading 0")
+        if self.contig_len.shape[0] != self.rs_off.shape[0] - 1:
+            raise ValueError("one contig length per replicate")
+        self.nmarkers, self.nsets, self.nreplicates = self.key_off.shape[0] - 1, self.ms_off.shape[0] - 1, self.rs_off.shape[0] - 1
+
+    def args(self):
+        """The ckm_sim_args of these arrays (it borrows them: keep this object alive over the call)."""
+        return SimArgs(self.nmarkers, self.key_off.ctypes.data, _ptr(self.key), self.key.shape[0],
+                       self.nsets, self.ms_off.ctypes.data, self.cs_off.ctypes.data, self.cs_off.shape[0] - 1, _ptr(self.cs_marker), self.cs_marker.shape[0],
+                       self.nreplicates, self.rs_off.ctypes.data, _ptr(self.starts), self.starts.shape[0], _ptr(self.contig_len))
+
+
+def sim_check(tables):
+    """ckm_sim_check: why the keys, the marker sets or the replicates of a call would be refused, without a device.  Raises CkmError as
+    sim_run would."""
+    a = tables.args()
+    _chk(load().ckm_sim_check(C.byref(a)))
+
+
+def sim_run(ctx, tables, budget_bytes=0):
+    """The simulation pass (ckm_sim_run) over all replicates of a call.  Returns a dict: out [nreplicates, nsets, 4] float64 (individual
+    completeness and contamination, set completeness and contamination, in percent), nrounds and the timings in ms."""
+    out = np.zeros((tables.nreplicates, tables.nsets, 4), dtype=np.float64)
+    info, a = SimInfo(), tables.args()
+    _chk(load().ckm_sim_run(ctx.h, C.byref(a), int(budget_bytes), _ptr(out), C.byref(info)))
+    return dict(out=out, nrounds=int(info.nrounds), **{f: getattr(info, f) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")})

@@ -1,0 +1,85 @@
+// kernels_sim.hip -- the marker-set simulation on the device (scripts/simulation.py of the reference, worker :97-142: per draw of contigs
+// MarkerSetBuilder.containedMarkerGenes, markerSetBuilder.py:353-369, then MarkerSet.genomeCheck, checkm/markerSets.py:206-238, in both
+// modes for every marker set).  gfx950 only.  The layout and the arithmetic are sim_dev.h, shared with the host executor of the CPU
+// tests; the float operations are IEEE double divisions, multiplications and additions in the reference's order (the library's
+// -ffp-contract=off -fno-fast-math).
+//
+//   sim_kernel   a block of four wavefronts per replicate; one launch covers the replicates of a round.
+//                1. The replicate's sorted starts are staged in LDS (STAGE_STARTS of them; a longer list stays in global memory and is
+//                   searched there by the same code).
+//                2. A lane owns a marker and walks its copies: two binary searches per copy.  The U counts stay in LDS (STAGE_COUNTS of
+//                   them; more go to the block's scratch row in global memory).  The searches of neighbouring lanes land on unrelated
+//                   banks: their conflicts are the price of a search and are not laid out away.
+//                3. A wavefront owns a marker set: sixty-four co-located sets at a time, a lane forms the two quotients of its set, then
+//                   every lane adds the sixty-four terms in list order (a broadcast read of lane l's registers), so lane 0 holds the
+//                   reference's sums.  The integer sums of the individual mode go through a butterfly over the wavefront.
+//                No atomics; every output word has one writer.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "sim_dev.h"
+
+namespace ckm {
+using namespace sim;
+
+struct SimDev {
+  const uint32_t *key_off;      // [U + 1]
+  const int32_t *key;
+  const uint32_t *ms_off;       // [S + 1]
+  const uint32_t *cs_off, *cs_marker, *num_markers;      // num_markers [S]
+  uint32_t U, S;
+};
+
+__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, WAVE);
+  return v;
+}
+
+// replicate r0 + blockIdx.x of the call; starts holds the round's starts, the first of them being entry start_base of the call's list;
+// scratch [blocks][U] only when U > STAGE_COUNTS; out [blocks][S][4]
+__global__ __launch_bounds__(THREADS) void sim_kernel(SimDev T, uint32_t r0, const uint64_t *__restrict__ rs_off, uint64_t start_base, const int32_t *__restrict__ starts,
+                                                       const int32_t *__restrict__ contig_len, uint32_t *__restrict__ scratch, double *__restrict__ out) {
+  __shared__ int32_t sStarts[STAGE_STARTS];
+  __shared__ uint32_t sCounts[STAGE_COUNTS];
+  const uint32_t r = r0 + blockIdx.x;
+  const uint64_t o = rs_off[r];
+  const uint32_t n = (uint32_t)(rs_off[r + 1] - o);
+  const int32_t *mine = starts + (o - start_base);
+  const bool staged = n <= STAGE_STARTS;
+  if (staged)
+    for (uint32_t k = threadIdx.x; k < n; k += THREADS) sStarts[k] = mine[k];
+  __syncthreads();
+  const int32_t *s = staged ? sStarts : mine;
+  uint32_t *counts = T.U <= STAGE_COUNTS ? sCounts : scratch + (uint64_t)blockIdx.x * T.U;
+  const int32_t len = contig_len[r];
+  for (uint32_t m = threadIdx.x; m < T.U; m += THREADS) counts[m] = marker_count(T.key, T.key_off[m], T.key_off[m + 1], s, n, len);
+  __syncthreads();                                              // the counts, in LDS or in the block's own scratch row
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  for (uint32_t ms = threadIdx.x >> 6; ms < T.S; ms += WAVES) {
+    const uint32_t c0 = T.ms_off[ms], c1 = T.ms_off[ms + 1];
+    Individual ind = {0u, 0ull};
+    double comp = 0.0, cont = 0.0;
+    for (uint32_t base = c0; base < c1; base += WAVE) {
+      const uint32_t c = base + (uint32_t)lane;
+      double tc = 0.0, tn = 0.0;
+      if (c < c1) set_terms(T.cs_marker, T.cs_off[c], T.cs_off[c + 1], counts, tc, tn, ind);
+      const int here = c1 - base < (uint32_t)WAVE ? (int)(c1 - base) : WAVE;
+      for (int l = 0; l < here; ++l) {                          // list order; the same in every lane
+        comp += __shfl(tc, l, WAVE);
+        cont += __shfl(tn, l, WAVE);
+      }
+    }
+    ind.present = (uint32_t)wave_sum(ind.present);
+    ind.multi = wave_sum(ind.multi);
+    if (lane == 0) finish(ind, T.num_markers[ms], comp, cont, c1 - c0, out + ((uint64_t)blockIdx.x * T.S + ms) * 4);
+  }
+}
+
+void launch_sim(hipStream_t st, const SimDev &T, uint32_t r0, uint32_t nr, const uint64_t *rs_off, uint64_t start_base, const int32_t *starts, const int32_t *contig_len,
+                uint32_t *scratch, double *out) {
+  if (!nr || !T.S) return;
+  hipLaunchKernelGGL(sim_kernel, dim3(nr), dim3(THREADS), 0, st, T, r0, rs_off, start_base, starts, contig_len, scratch, out);
+}
+
+}  // namespace ckm

@@ -12,9 +12,13 @@ methods raise: there is no other compute path.
 The reference's lists came out in the order of Python 2's dicts.  Here they are defined: colocatedGenes returns its pair strings
 sorted, colocatedSets its sets sorted by their smallest member.  Equality with the reference is equality of sets.  DESIGN section 21.
 
-The simulation and tree-walking methods of the script (sampleGenome*, buildBinMarkerSet, ...) are not here."""
+The simulation methods of the script (:265-369) are here as plain Python with the reference's results -- uniformity, sampleGenome,
+sampleGenomeScaffoldsInvLength, sampleGenomeScaffoldsWithoutReplacement, containedMarkerGenes -- and genomeChecks scores every marker set
+on every draw of a genome with one device call (kernels_sim.hip).  markerGenesOnScaffolds and the tree-walking
+methods (buildBinMarkerSet, ...) are not here."""
 from collections import defaultdict
 import logging
+import random
 import time
 
 import numpy as np
@@ -100,6 +104,7 @@ class MarkerSetBuilder(object):
         self.img = img
         self.cachedGeneCountTable = None
         self.last_timing = {}
+        self.last_sim_timing = {}
 
     def precomputeGenomeSeqLens(self, genomeIds):
         self.img.precomputeGenomeSeqLens(genomeIds)
@@ -328,3 +333,132 @@ class MarkerSetBuilder(object):
             for row, k in enumerate(device):
                 ml = mlists[row]
                 pairs[k] = sorted(_pair_name(res.families[ml[pi[x]]], res.families[ml[pj[x]]]) for x in range(off[row], off[row + 1]))
+
+    # ---- the simulation (markerSetBuilder.py:265-369) ---------------------------------------------------------------------------------------
+    def uniformity(self, genomeSize, pts):
+        """1 - sum |d - U| / sum max(d, U) over the gaps d of the sorted points, U the gap of len(pts) evenly spaced points."""
+        U = float(genomeSize) / (len(pts) + 1)
+        pts = sorted(pts)
+        num = den = 0
+        for a, b in zip(pts, pts[1:]):
+            num += abs(b - a - U)
+            den += max(b - a, U)
+        return 1.0 - num / den
+
+    def sampleGenome(self, genomeLen, percentComp, percentCont, contigLen):
+        """A draw of fixed-length contigs: (true completeness, true contamination, sorted contig starts).  Completeness contigs come
+        from random.sample, contamination contigs (with replacement) from numpy's legacy choice, in that order, so a caller that seeds
+        both generators gets the reference's contigs.  contigsInGenome is the integer quotient of the reference's Python 2 text."""
+        contigsInGenome = genomeLen // contigLen
+        nComp = int(contigsInGenome * percentComp + 0.5)
+        nCont = int(contigsInGenome * percentCont + 0.5)
+        compContigs = random.sample(range(contigsInGenome), nComp)
+        contContigs = np.random.choice(range(contigsInGenome), nCont, replace=True).tolist()
+        contigStarts = sorted(c * contigLen for c in compContigs + contContigs)
+        return float(nComp) * contigLen * 100 / genomeLen, float(nCont) * contigLen * 100 / genomeLen, contigStarts
+
+    @staticmethod
+    def _take_until(order, targetPer, seqLens, genomeSize):
+        sampled, truePer = [], 0.0
+        for seqId in order:
+            sampled.append(seqId)
+            truePer += float(seqLens[seqId]) / genomeSize
+            if truePer >= targetPer:
+                break
+        return sampled, truePer * 100
+
+    def sampleGenomeScaffoldsInvLength(self, targetPer, seqLens, genomeSize):
+        """Sequences drawn without replacement with probability inversely proportional to their length, until they hold targetPer of
+        the genome: (sequence ids, percentage held).  The probabilities are normalised with Python's own sum, as in the reference."""
+        seqProb = np.array([1.0 / (float(seqLen) / genomeSize) for seqLen in seqLens.values()])
+        seqProb /= sum(seqProb)
+        return self._take_until(np.random.choice(list(seqLens.keys()), size=len(seqLens), replace=False, p=seqProb), targetPer, seqLens, genomeSize)
+
+    def sampleGenomeScaffoldsWithoutReplacement(self, targetPer, seqLens, genomeSize):
+        """Sequences drawn uniformly without replacement until they hold targetPer of the genome: (sequence ids, percentage held)."""
+        return self._take_until(np.random.choice(list(seqLens.keys()), size=len(seqLens), replace=False), targetPer, seqLens, genomeSize)
+
+    def containedMarkerGenes(self, markerGenes, clusterIdToGenomePositions, startPartialGenomeContigs, contigLen):
+        """marker -> the contig starts s with 0 <= p[0] - s < contigLen, once per copy p and start s; markers without one are left out.
+        The plain loop: what genomeChecks runs in place of the device for a call the library refuses, and what it is tested against."""
+        contained = {}
+        for markerGene in markerGenes:
+            containedPos = [s for p in clusterIdToGenomePositions.get(markerGene, []) for s in startPartialGenomeContigs if 0 <= p[0] - s < contigLen]
+            if containedPos:
+                contained[markerGene] = containedPos
+        return contained
+
+    @staticmethod
+    def _genome_check_host(ms, hits):
+        """Both modes of MarkerSet.genomeCheck (checkm/markerSets.py:206-238) for one marker set on the host, in its operation order:
+        (individual completeness, individual contamination, set completeness, set contamination)."""
+        present = multiCopy = 0
+        for marker in ms.getMarkerGenes():
+            if marker in hits:
+                present += 1
+                multiCopy += len(hits[marker]) - 1
+        numMarkers = ms.numMarkers()
+        indComp, indCont = 100 * float(present) / numMarkers, 100 * float(multiCopy) / numMarkers
+        comp = cont = 0.0
+        for cs in ms.markerSet:
+            present = multiCopy = 0
+            for marker in cs:
+                count = len(hits.get(marker, []))
+                if count >= 1:
+                    present += 1
+                    multiCopy += count - 1
+            comp += float(present) / len(cs)
+            cont += float(multiCopy) / len(cs)
+        return indComp, indCont, 100 * comp / len(ms.markerSet), 100 * cont / len(ms.markerSet)
+
+    def _genome_checks_host(self, markerSets, genePositions, contigStartLists, contigLens):
+        out = np.zeros((len(contigStartLists), len(markerSets), 4), dtype=np.float64)
+        for r, (starts, contigLen) in enumerate(zip(contigStartLists, contigLens)):
+            for s, ms in enumerate(markerSets):
+                out[r, s] = self._genome_check_host(ms, self.containedMarkerGenes(ms.getMarkerGenes(), genePositions, starts, contigLen))
+        return out
+
+    @staticmethod
+    def _sim_tables(markerSets, genePositions, contigStartLists, contigLens):
+        """The arrays of one ckm_sim_run call (include/checkm_hip.h), or None where they cannot be said in int64: the distinct markers of
+        all sets sorted by name, their copies' starts, the marker sets as lists of co-located sets, the draws with their starts sorted."""
+        from checkm_amd import _lib
+        markers = sorted(set(m for ms in markerSets for m in ms.getMarkerGenes()))
+        midx = {m: k for k, m in enumerate(markers)}
+        copies = [[p[0] for p in genePositions.get(m, [])] for m in markers]
+        flat = [x for c in copies for x in c] + list(contigLens)
+        if not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) and -(1 << 63) <= x < (1 << 63) for x in flat):
+            return None
+        starts = [np.asarray(s).reshape(-1) for s in contigStartLists]
+        if not all(s.size == 0 or (s.dtype.kind in 'iu' and s.dtype.itemsize <= 8 and s.dtype != np.uint64) for s in starts):
+            return None
+        off = lambda lens: np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(lens, dtype=np.uint64)])
+        sets = [list(cs) for ms in markerSets for cs in ms.markerSet]
+        return _lib.SimTables(off([len(c) for c in copies]), [x for c in copies for x in c], off([len(ms.markerSet) for ms in markerSets]), off([len(cs) for cs in sets]),
+                              [midx[m] for cs in sets for m in cs], off([s.size for s in starts]),
+                              np.concatenate([np.sort(s.astype(np.int64)) for s in starts]) if starts else [], list(contigLens))
+
+    def genomeChecks(self, markerSets, genePositions, contigStartLists, contigLens):
+        """out[replicate][markerSet] = (individual completeness, individual contamination, set completeness, set contamination): for
+        every draw (contigStartLists[r], contigLens[r]) and marker set what containedMarkerGenes followed by MarkerSet.genomeCheck in
+        both modes gives, from ONE device call.  genePositions is geneDistTable[genomeId].  A call the library refuses (a position
+        beyond int32, a marker set without sets -- the reference's ZeroDivisionError) runs the plain loop."""
+        markerSets = list(markerSets)
+        if len(contigStartLists) != len(contigLens):
+            raise ValueError('one contig length per draw')
+        t = dict(pack=0.0, copy_in=0.0, kernel=0.0, copy_out=0.0, rounds=0, device=False)
+        self.last_sim_timing = t
+        from checkm_amd import _lib
+        t0 = time.perf_counter()
+        tables = self._sim_tables(markerSets, genePositions, contigStartLists, contigLens)
+        if tables is not None:
+            try:
+                _lib.sim_check(tables)
+            except _lib.CkmError:
+                tables = None
+        t['pack'] = time.perf_counter() - t0
+        if tables is None:
+            return self._genome_checks_host(markerSets, genePositions, contigStartLists, contigLens)
+        r = _lib.sim_run(self._ctx(), tables)
+        t.update(pack=t['pack'] + r['ms_pack'] / 1e3, copy_in=r['ms_upload'] / 1e3, kernel=r['ms_kernel'] / 1e3, copy_out=r['ms_download'] / 1e3, rounds=r['nrounds'], device=True)
+        return r['out']

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12 */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_* */
 
 enum {
   CKM_OK      =  0,
@@ -753,6 +753,45 @@ int  ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_t nqueries
                         const uint32_t *qm, double dist_threshold, double genome_threshold, uint64_t budget_bytes, ckm_mset_result **out);
 int  ckm_mset_columns_get(const ckm_mset_result *r, ckm_mset_columns *out);
 void ckm_mset_result_free(ckm_mset_result *r);
+
+/* ---- Simulation: marker sets scored on sampled genomes (additions to ABI 12) -------------------------------------------------
+ * Replaces the loop nest of scripts/simulation.py's worker (:97-142): per draw of contigs MarkerSetBuilder.containedMarkerGenes
+ * (scripts/genometreeworkflow/markerSetBuilder.py:353-369) and both modes of MarkerSet.genomeCheck (checkm/markerSets.py:206-238) for
+ * every marker set.  checkm_amd/csrc/sim_dev.h, kernels_sim.hip.
+ *
+ * Keys: for the nmarkers distinct markers of all marker sets of the call, key[key_off[m] .. key_off[m + 1] - 1] are the start positions
+ * p[0] of the copies of marker m in the test genome (nkeys entries in all; a marker without a copy has none).
+ * Marker sets: marker set s holds the co-located sets ms_off[s] .. ms_off[s + 1] - 1; co-located set c holds the marker indices
+ * cs_marker[cs_off[c] .. cs_off[c + 1] - 1] (ncs co-located sets, cs_off with ncs + 1 entries, nmembers entries of cs_marker).  A marker may
+ * sit in two co-located sets of one marker set: numMarkers() counts it twice, the individual mode once, as in the reference.
+ * Replicates: replicate r is the contig starts starts[rs_off[r] .. rs_off[r + 1] - 1], ascending, duplicates allowed, and contig_len[r].
+ * Every offset table starts at 0 and never falls.
+ *
+ * A copy at p counts once for every start s with 0 <= p - s < contig_len; a marker's count is the sum over its copies.  out holds four
+ * float64 per (replicate, marker set), out[(r * nsets + s) * 4 ..], in the reference's operation order:
+ *   100 * float(present) / numMarkers, 100 * float(multiCopy) / numMarkers      genomeCheck(hits, bIndividualMarkers=True)
+ *   100 * comp / nSets, 100 * cont / nSets                                      genomeCheck(hits, bIndividualMarkers=False)
+ * One launch covers the replicates of a round; a call goes in rounds of whole replicates within budget_bytes (0: CKM_SIM_BATCH_MB,
+ * default 256, << 20; a round holds at least one replicate), which never changes a result.  info may be NULL.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, an offset table that does not start at 0, falls or points beyond its table,
+ * a marker index beyond the keys, starts that are not ascending within a replicate, a co-located set without a member, a marker set
+ * without a co-located set (the reference divides by zero there); CKM_ERANGE for a key or a start outside [0, 2^31), a contig_len outside
+ * [1, 2^31), more than 2^24 markers or replicates, more than 2^20 marker sets, copies of a marker times starts of a replicate beyond
+ * 2^31 - 1.  ckm_sim_check applies the same tests and needs no device: the caller then computes such a call with its own loop. */
+typedef struct {
+  uint32_t        nmarkers;    const uint64_t *key_off;  const int64_t *key;        uint64_t nkeys;
+  uint32_t        nsets;       const uint64_t *ms_off;   const uint64_t *cs_off;    uint64_t ncs;
+  const uint32_t *cs_marker;   uint64_t        nmembers;
+  uint32_t        nreplicates; const uint64_t *rs_off;   const int64_t *starts;     uint64_t nstarts;
+  const int64_t  *contig_len;
+} ckm_sim_args;
+typedef struct {
+  uint64_t nrounds;
+  double   ms_pack, ms_upload, ms_kernel, ms_download, ms_total;   /* host packing; HIP events per phase; wall of the call */
+} ckm_sim_info;
+int  ckm_sim_check(const ckm_sim_args *a);
+int  ckm_sim_run(ckm_ctx *ctx, const ckm_sim_args *a, uint64_t budget_bytes, double *out, ckm_sim_info *info);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
