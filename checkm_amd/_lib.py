@@ -203,6 +203,26 @@ class SimInfo(C.Structure):
     _fields_ = [("nrounds", C.c_uint64)] + [(f, C.c_double) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")]
 
 
+class PlaceArgs(C.Structure):
+    _fields_ = [("nnodes", C.c_uint32), ("child_off", C.c_void_p), ("child", C.c_void_p), ("nchild", C.c_uint64), ("length", C.c_void_p),
+                ("nsites", C.c_uint32), ("nrows", C.c_uint32), ("row_off", C.c_void_p), ("rows", C.c_void_p), ("nrow_bytes", C.c_uint64),
+                ("nqueries", C.c_uint32), ("q_off", C.c_void_p), ("queries", C.c_void_p), ("nquery_bytes", C.c_uint64),
+                ("nrates", C.c_uint32), ("weights", C.c_void_p), ("U", C.c_void_p), ("Uinv", C.c_void_p), ("pi", C.c_void_p),
+                ("exp_len", C.c_void_p), ("exp_half", C.c_void_p), ("nfrac", C.c_uint32), ("exp_dist", C.c_void_p),
+                ("npend", C.c_uint32), ("exp_pend", C.c_void_p), ("max_pitches", C.c_uint32)]
+
+
+class PlaceOut(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("top_edge", "scan_m", "scan_e", "ref_m", "ref_e", "ref_f", "ref_g")]
+
+
+_PLACE_MS = ("ms_pack", "ms_upload", "ms_matrices", "ms_sweeps", "ms_tables", "ms_scan", "ms_topk", "ms_refine", "ms_download", "ms_total")
+
+
+class PlaceInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("nchunks", "chunk_sites", "nlevels_up", "nlevels_down")] + [(f, C.c_double) for f in _PLACE_MS]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -241,7 +261,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_fasta_ids_read", "ckm_fasta_ids_view_get", "ckm_fasta_ids_free", "ckm_unbinned_select", "ckm_unbinned_count", "ckm_unbinned_write",
            "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
-           "ckm_sim_check", "ckm_sim_run",
+           "ckm_sim_check", "ckm_sim_run", "ckm_place_check", "ckm_place_run",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -376,6 +396,8 @@ def load():
     L.ckm_mset_result_free.restype = None
     L.ckm_sim_check.argtypes = [C.POINTER(SimArgs)]
     L.ckm_sim_run.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_uint64, C.c_void_p, C.POINTER(SimInfo)]
+    L.ckm_place_check.argtypes = [C.POINTER(PlaceArgs)]
+    L.ckm_place_run.argtypes = [C.c_void_p, C.POINTER(PlaceArgs), C.c_uint64, C.POINTER(PlaceOut), C.POINTER(PlaceInfo)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1552,3 +1574,67 @@ def sim_run(ctx, tables, budget_bytes=0):
     info, a = SimInfo(), tables.args()
     _chk(load().ckm_sim_run(ctx.h, C.byref(a), int(budget_bytes), _ptr(out), C.byref(info)))
     return dict(out=out, nrounds=int(info.nrounds), **{f: getattr(info, f) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")})
+
+
+class PlaceTables(object):
+    """The arrays of one placement call as ckm_place_check / ckm_place_run take them (include/checkm_hip.h): the tree as children lists
+    (child_off / child) with the length of the edge above every node, the reference alignment (one row of bytes per leaf, ascending node
+    order) and the queries with their offsets, the rate weights, the eigenvectors U / Uinv, the frequencies pi and the host-made tables
+    of exponentials exp_len [N, R, 20], exp_half [N, R, 20], exp_dist [N, F, 2, R, 20] and exp_pend [1 + G, R, 20]."""
+
+    def __init__(self, child_off, child, length, nsites, row_off, rows, q_off, queries, weights, U, Uinv, pi, exp_len, exp_half, exp_dist, exp_pend, max_pitches):
+        u64 = lambda x: np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+        f64 = lambda x: np.ascontiguousarray(x, dtype=np.float64)
+        u8 = lambda x: np.ascontiguousarray(np.frombuffer(x, dtype=np.uint8) if isinstance(x, (bytes, bytearray)) else x, dtype=np.uint8).reshape(-1)
+        self.child_off, self.row_off, self.q_off = u64(child_off), u64(row_off), u64(q_off)
+        self.child = np.ascontiguousarray(child, dtype=np.uint32).reshape(-1)
+        self.length, self.weights, self.U, self.Uinv, self.pi = f64(length).reshape(-1), f64(weights).reshape(-1), f64(U), f64(Uinv), f64(pi).reshape(-1)
+        self.rows, self.queries = u8(rows), u8(queries)
+        self.exp_len, self.exp_half, self.exp_dist, self.exp_pend = f64(exp_len), f64(exp_half), f64(exp_dist), f64(exp_pend)
+        if not (self.child_off.size and self.row_off.size and self.q_off.size):
+            raise ValueError("an offset table holds at least its leading 0")
+        self.nnodes, self.nrows, self.nqueries = self.child_off.shape[0] - 1, self.row_off.shape[0] - 1, self.q_off.shape[0] - 1
+        self.nsites, self.nrates, self.max_pitches = int(nsites), self.weights.shape[0], int(max_pitches)
+        if self.length.shape[0] != self.nnodes or self.U.shape != (20, 20) or self.Uinv.shape != (20, 20) or self.pi.shape[0] != 20:
+            raise ValueError("one length per node, 20 x 20 eigenvectors and 20 frequencies")
+        if self.exp_len.shape != (self.nnodes, self.nrates, 20) or self.exp_half.shape != self.exp_len.shape:
+            raise ValueError("exp_len and exp_half are [nodes, rates, 20]")
+        if self.exp_dist.ndim != 5 or self.exp_dist.shape[:1] + self.exp_dist.shape[2:] != (self.nnodes, 2, self.nrates, 20):
+            raise ValueError("exp_dist is [nodes, fractions, 2, rates, 20]")
+        if self.exp_pend.ndim != 3 or self.exp_pend.shape[0] < 1 or self.exp_pend.shape[1:] != (self.nrates, 20):
+            raise ValueError("exp_pend is [1 + pendant lengths, rates, 20]")
+        self.nfrac, self.npend = self.exp_dist.shape[1], self.exp_pend.shape[0] - 1
+
+    def args(self):
+        """The ckm_place_args of these arrays (it borrows them: keep this object alive over the call)."""
+        return PlaceArgs(self.nnodes, self.child_off.ctypes.data, _ptr(self.child), self.child.shape[0], _ptr(self.length),
+                         self.nsites, self.nrows, self.row_off.ctypes.data, _ptr(self.rows), self.rows.shape[0],
+                         self.nqueries, self.q_off.ctypes.data, _ptr(self.queries), self.queries.shape[0],
+                         self.nrates, _ptr(self.weights), _ptr(self.U), _ptr(self.Uinv), _ptr(self.pi), _ptr(self.exp_len), _ptr(self.exp_half),
+                         self.nfrac, _ptr(self.exp_dist), self.npend, _ptr(self.exp_pend), self.max_pitches)
+
+    def outputs(self):
+        """Fresh output arrays [nqueries, max_pitches] and the ckm_place_out over them."""
+        shape = (self.nqueries, self.max_pitches)
+        o = dict(top_edge=np.full(shape, -1, dtype=np.int32), scan_m=np.zeros(shape), scan_e=np.zeros(shape, dtype=np.int64), ref_m=np.zeros(shape),
+                 ref_e=np.zeros(shape, dtype=np.int64), ref_f=np.full(shape, -1, dtype=np.int32), ref_g=np.full(shape, -1, dtype=np.int32))
+        return o, PlaceOut(*[_ptr(o[f]) for f in ("top_edge", "scan_m", "scan_e", "ref_m", "ref_e", "ref_f", "ref_g")])
+
+
+def place_check(tables):
+    """ckm_place_check: why the tree, the alignment, the queries or the tables of a call would be refused, without a device.  Raises
+    CkmError as place_run would."""
+    a = tables.args()
+    _chk(load().ckm_place_check(C.byref(a)))
+
+
+def place_run(ctx, tables, budget_bytes=0):
+    """The placement pass (ckm_place_run).  Returns a dict: per (query, kept slot) top_edge (int32, -1 beyond the edges), the scan's
+    likelihood scan_m * 2^scan_e, the refined ref_m * 2^ref_e with the grid indices ref_f / ref_g; nchunks, chunk_sites, the numbers of
+    sweep levels and the timings in ms."""
+    o, po = tables.outputs()
+    info, a = PlaceInfo(), tables.args()
+    _chk(load().ckm_place_run(ctx.h, C.byref(a), int(budget_bytes), C.byref(po), C.byref(info)))
+    o.update({f: int(getattr(info, f)) for f in ("nchunks", "chunk_sites", "nlevels_up", "nlevels_down")})
+    o.update({f: getattr(info, f) for f in _PLACE_MS})
+    return o

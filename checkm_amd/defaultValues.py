@@ -24,6 +24,14 @@ class DefaultValues(object):
     SELECTED_MARKER_SETS = os.path.join(CHECKM_DATA_DIR, 'selected_marker_sets.tsv')
     TAXON_MARKER_SETS = os.path.join(CHECKM_DATA_DIR, 'taxon_marker_sets.tsv')
     DISTRIBUTION_DIR = os.path.join(CHECKM_DATA_DIR, 'distributions')
+    GENOME_TREE_DIR = os.path.join(CHECKM_DATA_DIR, 'genome_tree')
+    PPLACER_REF_PACKAGE_FULL = os.path.join(GENOME_TREE_DIR, 'genome_tree_full.refpkg')
+    PPLACER_REF_PACKAGE_REDUCED = os.path.join(GENOME_TREE_DIR, 'genome_tree_reduced.refpkg')
+    GENOME_TREE = 'genome_tree.tre'
+    PPLACER_CONCAT_SEQ_OUT = 'concatenated.fasta'
+    PPLACER_JSON_OUT = 'concatenated.pplacer.json'
+    PPLACER_OUT = 'pplacer.out'
+    PPLACER_TREE_OUT = 'concatenated.tre'
 
     PHYLO_HMM_MODEL_INFO = 'phylo_hmm_info.pkl.gz'
     CHECKM_HMM_MODEL_INFO = 'checkm_hmm_info.pkl.gz'
@@ -49,3 +57,6 @@ class DefaultValues(object):
         cls.SELECTED_MARKER_SETS = os.path.join(root, 'selected_marker_sets.tsv')
         cls.TAXON_MARKER_SETS = os.path.join(root, 'taxon_marker_sets.tsv')
         cls.DISTRIBUTION_DIR = os.path.join(root, 'distributions')
+        cls.GENOME_TREE_DIR = os.path.join(root, 'genome_tree')
+        cls.PPLACER_REF_PACKAGE_FULL = os.path.join(cls.GENOME_TREE_DIR, 'genome_tree_full.refpkg')
+        cls.PPLACER_REF_PACKAGE_REDUCED = os.path.join(cls.GENOME_TREE_DIR, 'genome_tree_reduced.refpkg')

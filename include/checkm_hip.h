@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_* */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_* and ckm_place_* */
 
 enum {
   CKM_OK      =  0,
@@ -792,6 +792,47 @@ typedef struct {
 } ckm_sim_info;
 int  ckm_sim_check(const ckm_sim_args *a);
 int  ckm_sim_run(ckm_ctx *ctx, const ckm_sim_args *a, uint64_t budget_bytes, double *out, ckm_sim_info *info);
+
+/* ---- PplacerRunner: bins placed on the edges of the reference tree (additions to ABI 12) -------------------------------------
+ * Replaces the pplacer call of checkm/pplacer.py:70-80 by a grid search on the device.  checkm_amd/csrc/place_dev.h, kernels_place.hip.
+ *
+ * Tree: nnodes nodes; node v has the children child[child_off[v] .. child_off[v + 1] - 1] (nchild entries in all), none (a leaf) or at
+ * least two; the root, the one node nobody lists, has two or three.  length[v] is the length of the edge above v (the root's is not
+ * read).  Edge numbers are node numbers.  Alignment: one row per leaf in ascending node order, rows[row_off[k] .. row_off[k + 1] - 1],
+ * nsites characters each; queries likewise.  The 20 letters ARNDCQEGHILKMFPSTWYV are states, every other byte is "unknown".
+ * Model: P(t)[i][j] = max(0, sum_k U[i][k] e_k Uinv[k][j]) with the caller's tables of e_k = exp(lambda_k * rate * t), 20 per entry:
+ * exp_len[nnodes][nrates] (t = length), exp_half (length / 2), exp_dist[nnodes][nfrac][2][nrates] (f * length, (1 - f) * length),
+ * exp_pend[1 + npend][nrates] (startPend, then the pendant grid); weights[nrates], pi[20].  No exp and no log runs in the library.
+ *
+ * Per query the max_pitches best edges of the scan (midpoint, startPend), larger first, ties to the lower edge number, each refined
+ * over the grid (ties to the lower distal index, then the lower pendant index).  Outputs hold nqueries * max_pitches entries; entries
+ * beyond the number of edges have top_edge -1.  A likelihood is m * 2^e with m in [0.5, 1) (or m = 0).  The sites go in chunks of a
+ * multiple of 64 within budget_bytes (0: CKM_PLACE_BATCH_MB, default 2048, << 20; never fewer than 64 sites), which never changes a
+ * result.  info may be NULL.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, offsets that do not start at 0, fall or point beyond their table, a child
+ * listed twice, a node with one child, a root without two or three children, a cycle, a negative or non-finite length or table entry,
+ * an alignment row or query whose length is not nsites, an empty grid; CKM_ERANGE for more than 8 rates, more than 32 grid values,
+ * more than 2^22 nodes, sites or queries, max_pitches above 4096.  ckm_place_check applies the same tests and needs no device. */
+typedef struct {
+  uint32_t nnodes;    const uint64_t *child_off;  const uint32_t *child;   uint64_t nchild;       const double *length;
+  uint32_t nsites;    uint32_t nrows;             const uint64_t *row_off; const uint8_t *rows;   uint64_t nrow_bytes;
+  uint32_t nqueries;  const uint64_t *q_off;      const uint8_t *queries;  uint64_t nquery_bytes;
+  uint32_t nrates;    const double *weights;      const double *U;         const double *Uinv;    const double *pi;
+  const double *exp_len;  const double *exp_half;
+  uint32_t nfrac;     const double *exp_dist;
+  uint32_t npend;     const double *exp_pend;
+  uint32_t max_pitches;
+} ckm_place_args;
+typedef struct {
+  int32_t *top_edge;  double *scan_m;  int64_t *scan_e;  double *ref_m;  int64_t *ref_e;  int32_t *ref_f;  int32_t *ref_g;
+} ckm_place_out;
+typedef struct {
+  uint64_t nchunks, chunk_sites, nlevels_up, nlevels_down;
+  double   ms_pack, ms_upload, ms_matrices, ms_sweeps, ms_tables, ms_scan, ms_topk, ms_refine, ms_download, ms_total;
+} ckm_place_info;
+int  ckm_place_check(const ckm_place_args *a);
+int  ckm_place_run(ckm_ctx *ctx, const ckm_place_args *a, uint64_t budget_bytes, const ckm_place_out *out, ckm_place_info *info);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
