@@ -223,6 +223,26 @@ class PlaceInfo(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("nchunks", "chunk_sites", "nlevels_up", "nlevels_down")] + [(f, C.c_double) for f in _PLACE_MS]
 
 
+class NhmmArgs(C.Structure):
+    _fields_ = [("nmodels", C.c_uint32), ("M", C.c_void_p), ("tab_off", C.c_void_p), ("emis", C.c_void_p), ("trans", C.c_void_p), ("ntab", C.c_uint64),
+                ("min_score", C.c_void_p), ("stride", C.c_uint32), ("overlap", C.c_uint32), ("strands", C.c_uint32)]
+
+
+_NHMM_ROWS = ("row_model", "row_seq", "row_strand", "row_pos", "row_start", "row_score")
+_NHMM_HITS = ("hit_model", "hit_seq", "hit_strand", "hit_from", "hit_to", "hit_score")
+
+
+class NhmmColumns(C.Structure):
+    _fields_ = [("nrows", C.c_uint64)] + [(f, C.c_void_p) for f in _NHMM_ROWS] + [("nhits", C.c_uint64)] + [(f, C.c_void_p) for f in _NHMM_HITS]
+
+
+_NHMM_MS = ("ms_tables", "ms_upload", "ms_scan", "ms_compact", "ms_download", "ms_hits", "ms_total")
+
+
+class NhmmInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("tiles", "launches", "cells", "batches")] + [(f, C.c_double) for f in _NHMM_MS]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -262,6 +282,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
            "ckm_sim_check", "ckm_sim_run", "ckm_place_check", "ckm_place_run",
+           "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -398,6 +419,11 @@ def load():
     L.ckm_sim_run.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_uint64, C.c_void_p, C.POINTER(SimInfo)]
     L.ckm_place_check.argtypes = [C.POINTER(PlaceArgs)]
     L.ckm_place_run.argtypes = [C.c_void_p, C.POINTER(PlaceArgs), C.c_uint64, C.POINTER(PlaceOut), C.POINTER(PlaceInfo)]
+    L.ckm_nhmm_check.argtypes = [C.POINTER(NhmmArgs)]
+    L.ckm_nhmm_run.argtypes = [C.c_void_p, C.POINTER(NhmmArgs), C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(NhmmInfo)]
+    L.ckm_nhmm_columns_get.argtypes = [C.c_void_p, C.POINTER(NhmmColumns)]
+    L.ckm_nhmm_free.argtypes = [C.c_void_p]
+    L.ckm_nhmm_free.restype = None
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1638,3 +1664,59 @@ def place_run(ctx, tables, budget_bytes=0):
     o.update({f: int(getattr(info, f)) for f in ("nchunks", "chunk_sites", "nlevels_up", "nlevels_down")})
     o.update({f: getattr(info, f) for f in _PLACE_MS})
     return o
+
+
+class NhmmTables(object):
+    """The arrays of one model scan as ckm_nhmm_check / ckm_nhmm_run take them (include/checkm_hip.h): per model the int32 milli-bit
+    tables emis [4, M] (A C G T/U) and trans [7, M] (MM IM DM MI II MD DD, node k at index k - 1, the transitions into k holding node
+    k - 1's numbers) and the reporting threshold min_score; the tile geometry stride / overlap; strands (1 forward, 2 reverse, 3 both)."""
+
+    def __init__(self, models, min_score, stride, overlap, strands=3):
+        for e, t in models:
+            if e.ndim != 2 or t.ndim != 2 or e.shape[0] != 4 or t.shape[0] != 7 or t.shape[1] != e.shape[1]:
+                raise ValueError("a model is (emis [4, M], trans [7, M])")
+        self.M = np.ascontiguousarray([e.shape[1] for e, _ in models], dtype=np.uint32)
+        self.tab_off = np.concatenate([[0], np.cumsum(self.M, dtype=np.uint64)]).astype(np.uint64)
+        self.emis = np.ascontiguousarray(np.concatenate([np.asarray(e, dtype=np.int32).reshape(-1) for e, _ in models] or [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
+        self.trans = np.ascontiguousarray(np.concatenate([np.asarray(t, dtype=np.int32).reshape(-1) for _, t in models] or [np.zeros(0, dtype=np.int32)]), dtype=np.int32)
+        self.min_score = np.ascontiguousarray(min_score, dtype=np.int32).reshape(-1)
+        if self.min_score.shape[0] != len(models):
+            raise ValueError("one min_score per model")
+        self.nmodels, self.stride, self.overlap, self.strands = len(models), int(stride), int(overlap), int(strands)
+
+    def args(self):
+        """The ckm_nhmm_args of these arrays (it borrows them: keep this object alive over the call)."""
+        return NhmmArgs(self.nmodels, _ptr(self.M), self.tab_off.ctypes.data, _ptr(self.emis), _ptr(self.trans), int(self.tab_off[-1]), _ptr(self.min_score),
+                        self.stride, self.overlap, self.strands)
+
+
+def nhmm_columns(c, info):
+    """The dict nhmm_run returns, copied out of a filled NhmmColumns and an info object with the NhmmInfo field names."""
+    def col(p, n, dt):
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_int32 if dt == np.int32 else C.c_uint32)), shape=(n,)).copy() if n else np.zeros(0, dtype=dt)
+    o = {f: col(getattr(c, f), int(c.nrows), np.int32 if f.endswith("score") else np.uint32) for f in _NHMM_ROWS}
+    o.update({f: col(getattr(c, f), int(c.nhits), np.int32 if f.endswith("score") else np.uint32) for f in _NHMM_HITS})
+    o.update({f: int(getattr(info, f)) for f in ("tiles", "launches", "cells", "batches")})
+    o.update({f: float(getattr(info, f)) for f in _NHMM_MS})
+    return o
+
+
+def nhmm_check(tables):
+    """ckm_nhmm_check: why the models, the thresholds or the geometry of a call would be refused, without a device.  Raises CkmError as
+    nhmm_run would."""
+    a = tables.args()
+    _chk(load().ckm_nhmm_check(C.byref(a)))
+
+
+def nhmm_run(ctx, tables, seqs, budget_bytes=0):
+    """The model scan over a NucSeqs batch (ckm_nhmm_run).  Returns a dict: the reported rows (row_model, row_seq, row_strand, row_pos,
+    row_start in strand coordinates, row_score), the hits (hit_model, hit_seq, hit_strand, hit_from <= hit_to on the forward strand,
+    hit_score), tiles, launches, cells, batches and the timings in ms."""
+    h, info, a = C.c_void_p(), NhmmInfo(), tables.args()
+    _chk(load().ckm_nhmm_run(ctx.h, C.byref(a), seqs.h, int(budget_bytes), C.byref(h), C.byref(info)))
+    try:
+        c = NhmmColumns()
+        _chk(load().ckm_nhmm_columns_get(h, C.byref(c)))
+        return nhmm_columns(c, info)
+    finally:
+        load().ckm_nhmm_free(h)

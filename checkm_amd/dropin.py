@@ -108,3 +108,11 @@ def install():
     else:
         from checkm_amd import unbinned as ub
         checkm.unbinned.Unbinned = ub.Unbinned
+    # `checkm ssu_finder`: the three nucleotide models scanned on the device instead of three nhmmer runs
+    try:
+        import checkm.ssuFinder
+    except ImportError:
+        pass
+    else:
+        from checkm_amd import ssuFinder as sf
+        checkm.ssuFinder.SSU_Finder = sf.SSU_Finder

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_* and ckm_place_* */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_place_* and ckm_nhmm_* */
 
 enum {
   CKM_OK      =  0,
@@ -833,6 +833,41 @@ typedef struct {
 } ckm_place_info;
 int  ckm_place_check(const ckm_place_args *a);
 int  ckm_place_run(ckm_ctx *ctx, const ckm_place_args *a, uint64_t budget_bytes, const ckm_place_out *out, ckm_place_info *info);
+
+/* ---- SSU_Finder: nucleotide models scanned over both strands of every contig (additions to ABI 12) --------------------------
+ * Replaces the three nhmmer calls of checkm/ssuFinder.py:49-61 by a Viterbi scan of our own definition (checkm_amd/csrc/nhmm_dev.h states
+ * it: int32 milli-bit scores, cells (score, start), unihit local, tiles of `stride` rows that start `overlap` rows early), on the device
+ * in kernels_nhmm.hip.
+ *
+ * Model m has M[m] <= 2048 nodes; its tables start at node tab_off[m] of the call (tab_off[nmodels] == ntab): emis + 4 tab_off[m] is
+ * [4][M] (A C G T/U), trans + 7 tab_off[m] is [7][M] in the order MM IM DM MI II MD DD, node k at index k - 1, the transitions into k
+ * holding node k - 1's numbers of the file.  strands: 1 forward, 2 reverse complement, 3 both.  Every row i of a strand whose best cell
+ * scores at least min_score[m] is reported, in (model, sequence, strand, row) order: row_pos = i and row_start in strand coordinates
+ * (1-based).  Hits (nhmm_dev.h: groups by start, greedy by score) carry forward-strand coordinates hit_from <= hit_to.
+ * budget_bytes (0: CKM_SSU_BATCH_MB, default 256, << 20) bounds the row buffer of a launch, 8 bytes per owned row, and changes no result.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, a model without nodes, a tab_off that does not step by M, strands outside
+ * 1..3, a stride of 0, a sequence with a byte beyond ASCII (the message names it); CKM_ERANGE for M > 2048, a min_score below -2^20,
+ * an emission outside [-2^21, 2048], a transition outside [-2^21, 0], stride + overlap above 2^17, a sequence of 2^31 - 1 bytes or more.
+ * ckm_nhmm_check applies the tests of the arguments and needs no device. */
+typedef struct {
+  uint32_t nmodels;   const uint32_t *M;      const uint64_t *tab_off;   const int32_t *emis;   const int32_t *trans;   uint64_t ntab;
+  const int32_t *min_score;
+  uint32_t stride, overlap, strands;
+} ckm_nhmm_args;
+typedef struct ckm_nhmm_result ckm_nhmm_result;
+typedef struct {
+  uint64_t nrows;   const uint32_t *row_model, *row_seq, *row_strand, *row_pos, *row_start;   const int32_t *row_score;
+  uint64_t nhits;   const uint32_t *hit_model, *hit_seq, *hit_strand, *hit_from, *hit_to;     const int32_t *hit_score;
+} ckm_nhmm_columns;
+typedef struct {
+  uint64_t tiles, launches, cells, batches;
+  double   ms_tables, ms_upload, ms_scan, ms_compact, ms_download, ms_hits, ms_total;
+} ckm_nhmm_info;
+int  ckm_nhmm_check(const ckm_nhmm_args *a);
+int  ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucseq *seqs, uint64_t budget_bytes, ckm_nhmm_result **out, ckm_nhmm_info *info);
+int  ckm_nhmm_columns_get(const ckm_nhmm_result *r, ckm_nhmm_columns *out);
+void ckm_nhmm_free(ckm_nhmm_result *r);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
