@@ -203,6 +203,12 @@ class SimInfo(C.Structure):
     _fields_ = [("nrounds", C.c_uint64)] + [(f, C.c_double) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")]
 
 
+class SimScafArgs(C.Structure):
+    _fields_ = [("ngenomes", C.c_uint32), ("nscaf", C.c_void_p), ("nmarkers", C.c_uint32), ("sc_off", C.c_void_p), ("sc", C.c_void_p), ("nsc", C.c_uint64),
+                ("nsets", C.c_uint32), ("ms_off", C.c_void_p), ("cs_off", C.c_void_p), ("ncs", C.c_uint64), ("cs_marker", C.c_void_p), ("nmembers", C.c_uint64),
+                ("nreplicates", C.c_uint32), ("test", C.c_void_p), ("cont", C.c_void_p), ("bit_off", C.c_void_p), ("bits", C.c_void_p), ("nwords", C.c_uint64)]
+
+
 class PlaceArgs(C.Structure):
     _fields_ = [("nnodes", C.c_uint32), ("child_off", C.c_void_p), ("child", C.c_void_p), ("nchild", C.c_uint64), ("length", C.c_void_p),
                 ("nsites", C.c_uint32), ("nrows", C.c_uint32), ("row_off", C.c_void_p), ("rows", C.c_void_p), ("nrow_bytes", C.c_uint64),
@@ -281,7 +287,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_fasta_ids_read", "ckm_fasta_ids_view_get", "ckm_fasta_ids_free", "ckm_unbinned_select", "ckm_unbinned_count", "ckm_unbinned_write",
            "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
-           "ckm_sim_check", "ckm_sim_run", "ckm_place_check", "ckm_place_run",
+           "ckm_sim_check", "ckm_sim_run", "ckm_simscaf_check", "ckm_simscaf_run", "ckm_place_check", "ckm_place_run",
            "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
@@ -417,6 +423,8 @@ def load():
     L.ckm_mset_result_free.restype = None
     L.ckm_sim_check.argtypes = [C.POINTER(SimArgs)]
     L.ckm_sim_run.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_uint64, C.c_void_p, C.POINTER(SimInfo)]
+    L.ckm_simscaf_check.argtypes = [C.POINTER(SimScafArgs)]
+    L.ckm_simscaf_run.argtypes = [C.c_void_p, C.POINTER(SimScafArgs), C.c_uint64, C.c_void_p, C.POINTER(SimInfo)]
     L.ckm_place_check.argtypes = [C.POINTER(PlaceArgs)]
     L.ckm_place_run.argtypes = [C.c_void_p, C.POINTER(PlaceArgs), C.c_uint64, C.POINTER(PlaceOut), C.POINTER(PlaceInfo)]
     L.ckm_nhmm_check.argtypes = [C.POINTER(NhmmArgs)]
@@ -1599,6 +1607,51 @@ def sim_run(ctx, tables, budget_bytes=0):
     out = np.zeros((tables.nreplicates, tables.nsets, 4), dtype=np.float64)
     info, a = SimInfo(), tables.args()
     _chk(load().ckm_sim_run(ctx.h, C.byref(a), int(budget_bytes), _ptr(out), C.byref(info)))
+    return dict(out=out, nrounds=int(info.nrounds), **{f: getattr(info, f) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")})
+
+
+SIMSCAF_NONE = 0xffffffff
+
+
+class SimScafTables(object):
+    """The arrays of one scaffold-simulation call as ckm_simscaf_check / ckm_simscaf_run take them (include/checkm_hip.h): nscaf per
+    genome, sc_off / sc for the (genome, marker) cells, ms_off / cs_off / cs_marker for the marker sets, test / cont / bit_off / bits for
+    the replicates (cont SIMSCAF_NONE: no contaminant)."""
+
+    def __init__(self, nscaf, nmarkers, sc_off, sc, ms_off, cs_off, cs_marker, test, cont, bit_off, bits):
+        u64 = lambda x: np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+        u32 = lambda x: np.ascontiguousarray(x, dtype=np.uint32).reshape(-1)
+        self.nscaf, self.sc, self.cs_marker, self.test, self.cont, self.bits = u32(nscaf), u32(sc), u32(cs_marker), u32(test), u32(cont), u32(bits)
+        self.sc_off, self.ms_off, self.cs_off, self.bit_off = u64(sc_off), u64(ms_off), u64(cs_off), u64(bit_off)
+        self.ngenomes, self.nmarkers = self.nscaf.shape[0], int(nmarkers)
+        if not (self.ms_off.size and self.cs_off.size and self.bit_off.size):
+            raise ValueError("an offset table holds at least its leading 0")
+        if self.sc_off.shape[0] != self.ngenomes * self.nmarkers + 1:
+            raise ValueError("one offset per (genome, marker) cell and the end")
+        if not (self.test.shape[0] == self.cont.shape[0] == self.bit_off.shape[0] - 1):
+            raise ValueError("one test genome, one contaminant and one offset per replicate")
+        self.nsets, self.nreplicates = self.ms_off.shape[0] - 1, self.test.shape[0]
+
+    def args(self):
+        """The ckm_simscaf_args of these arrays (it borrows them: keep this object alive over the call)."""
+        return SimScafArgs(self.ngenomes, _ptr(self.nscaf), self.nmarkers, self.sc_off.ctypes.data, _ptr(self.sc), self.sc.shape[0],
+                           self.nsets, self.ms_off.ctypes.data, self.cs_off.ctypes.data, self.cs_off.shape[0] - 1, _ptr(self.cs_marker), self.cs_marker.shape[0],
+                           self.nreplicates, _ptr(self.test), _ptr(self.cont), self.bit_off.ctypes.data, _ptr(self.bits), self.bits.shape[0])
+
+
+def simscaf_check(tables):
+    """ckm_simscaf_check: why the tables, the marker sets or the replicates of a call would be refused, without a device.  Raises
+    CkmError as simscaf_run would."""
+    a = tables.args()
+    _chk(load().ckm_simscaf_check(C.byref(a)))
+
+
+def simscaf_run(ctx, tables, budget_bytes=0):
+    """The scaffold-simulation pass (ckm_simscaf_run) over all replicates of a call.  Returns a dict: out [nreplicates, nsets, 4] float64
+    (individual completeness and contamination, set completeness and contamination, in percent), nrounds and the timings in ms."""
+    out = np.zeros((tables.nreplicates, tables.nsets, 4), dtype=np.float64)
+    info, a = SimInfo(), tables.args()
+    _chk(load().ckm_simscaf_run(ctx.h, C.byref(a), int(budget_bytes), _ptr(out), C.byref(info)))
     return dict(out=out, nrounds=int(info.nrounds), **{f: getattr(info, f) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")})
 
 

@@ -10,13 +10,13 @@
 //                2. A lane owns a marker and walks its copies: two binary searches per copy.  The U counts stay in LDS (STAGE_COUNTS of
 //                   them; more go to the block's scratch row in global memory).  The searches of neighbouring lanes land on unrelated
 //                   banks: their conflicts are the price of a search and are not laid out away.
-//                3. A wavefront owns a marker set: sixty-four co-located sets at a time, a lane forms the two quotients of its set, then
-//                   every lane adds the sixty-four terms in list order (a broadcast read of lane l's registers), so lane 0 holds the
-//                   reference's sums.  The integer sums of the individual mode go through a butterfly over the wavefront.
+//                3. A wavefront owns a marker set and scores it from the counts (score_sets of sim_score.h, shared with
+//                   kernels_simscaf.hip): the quotients of the co-located sets summed in list order, the integers by butterfly.
 //                No atomics; every output word has one writer.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "sim_dev.h"
+#include "sim_score.h"
 
 namespace ckm {
 using namespace sim;
@@ -28,12 +28,6 @@ struct SimDev {
   const uint32_t *cs_off, *cs_marker, *num_markers;      // num_markers [S]
   uint32_t U, S;
 };
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
-#pragma unroll
-  for (int d = WAVE / 2; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, WAVE);
-  return v;
-}
 
 // replicate r0 + blockIdx.x of the call; starts holds the round's starts, the first of them being entry start_base of the call's list;
 // scratch [blocks][U] only when U > STAGE_COUNTS; out [blocks][S][4]
@@ -55,25 +49,8 @@ __global__ __launch_bounds__(THREADS) void sim_kernel(SimDev T, uint32_t r0, con
   for (uint32_t m = threadIdx.x; m < T.U; m += THREADS) counts[m] = marker_count(T.key, T.key_off[m], T.key_off[m + 1], s, n, len);
   __syncthreads();                                              // the counts, in LDS or in the block's own scratch row
 
-  const int lane = threadIdx.x & (WAVE - 1);
-  for (uint32_t ms = threadIdx.x >> 6; ms < T.S; ms += WAVES) {
-    const uint32_t c0 = T.ms_off[ms], c1 = T.ms_off[ms + 1];
-    Individual ind = {0u, 0ull};
-    double comp = 0.0, cont = 0.0;
-    for (uint32_t base = c0; base < c1; base += WAVE) {
-      const uint32_t c = base + (uint32_t)lane;
-      double tc = 0.0, tn = 0.0;
-      if (c < c1) set_terms(T.cs_marker, T.cs_off[c], T.cs_off[c + 1], counts, tc, tn, ind);
-      const int here = c1 - base < (uint32_t)WAVE ? (int)(c1 - base) : WAVE;
-      for (int l = 0; l < here; ++l) {                          // list order; the same in every lane
-        comp += __shfl(tc, l, WAVE);
-        cont += __shfl(tn, l, WAVE);
-      }
-    }
-    ind.present = (uint32_t)wave_sum(ind.present);
-    ind.multi = wave_sum(ind.multi);
-    if (lane == 0) finish(ind, T.num_markers[ms], comp, cont, c1 - c0, out + ((uint64_t)blockIdx.x * T.S + ms) * 4);
-  }
+  const SetsDev M = {T.ms_off, T.cs_off, T.cs_marker, T.num_markers, T.S};
+  score_sets(M, counts, out + (uint64_t)blockIdx.x * T.S * 4);
 }
 
 void launch_sim(hipStream_t st, const SimDev &T, uint32_t r0, uint32_t nr, const uint64_t *rs_off, uint64_t start_base, const int32_t *starts, const int32_t *contig_len,

@@ -115,6 +115,35 @@ struct Args {
   uint32_t nreplicates; const uint64_t *rs_off; const int64_t *starts, *contig_len;
 };
 
+// The marker sets of a call (ms_off / cs_off / cs_marker over nmarkers markers): offsets in order and within their tables, no marker set
+// without a co-located set, no co-located set without a member, every member a marker.  Shared with simscaf_dev.h.
+inline int check_marker_sets(uint32_t nmarkers, uint32_t nsets, const uint64_t *ms_off, const uint64_t *cs_off, const uint32_t *cs_marker, uint64_t ncs, uint64_t nmembers,
+                             std::string &why) {
+  auto no = [&](int kind, const std::string &m) { why = m; return kind; };
+  if (nsets > MAX_SETS) return no(ARGS_RANGE, "more than 2^20 marker sets");
+  if (!ms_off || !cs_off) return no(ARGS_INVALID, "NULL argument");
+  if (ms_off[0] != 0) return no(ARGS_INVALID, "ms_off does not start at 0");
+  for (uint32_t s = 0; s < nsets; ++s) {
+    if (ms_off[s + 1] < ms_off[s]) return no(ARGS_INVALID, "ms_off falls at marker set " + std::to_string(s));
+    if (ms_off[s + 1] > ncs) return no(ARGS_INVALID, "ms_off beyond the co-located sets at marker set " + std::to_string(s));
+    if (ms_off[s + 1] == ms_off[s]) return no(ARGS_INVALID, "marker set " + std::to_string(s) + " has no sets");
+  }
+  const uint64_t used_cs = ms_off[nsets];
+  if (used_cs > MAX_MEMBERS) return no(ARGS_RANGE, "more than 2^31 - 1 co-located sets");
+  if (cs_off[0] != 0) return no(ARGS_INVALID, "cs_off does not start at 0");
+  for (uint64_t c = 0; c < used_cs; ++c) {
+    if (cs_off[c + 1] < cs_off[c]) return no(ARGS_INVALID, "cs_off falls at co-located set " + std::to_string(c));
+    if (cs_off[c + 1] > nmembers) return no(ARGS_INVALID, "cs_off beyond the members at co-located set " + std::to_string(c));
+    if (cs_off[c + 1] == cs_off[c]) return no(ARGS_INVALID, "co-located set " + std::to_string(c) + " is empty");
+  }
+  const uint64_t used_members = cs_off[used_cs];
+  if (used_members > MAX_MEMBERS) return no(ARGS_RANGE, "more than 2^31 - 1 members of co-located sets");
+  if (used_members && !cs_marker) return no(ARGS_INVALID, "NULL members");
+  for (uint64_t e = 0; e < used_members; ++e)
+    if (cs_marker[e] >= nmarkers) return no(ARGS_INVALID, "marker index " + std::to_string(cs_marker[e]) + " beyond the keys");
+  return ARGS_OK;
+}
+
 // Why a call is refused.  No table is indexed before the offsets into it are known to be in order and within it: ncs and nmembers are
 // what the caller's cs_off and cs_marker hold (the library's entries take them from the caller, the tables themselves cannot say).
 inline int check(const Args &a, uint64_t ncs, uint64_t nmembers, uint64_t nkeys, uint64_t nstarts, std::string &why) {
@@ -136,25 +165,7 @@ inline int check(const Args &a, uint64_t ncs, uint64_t nmembers, uint64_t nkeys,
   for (uint64_t k = 0; k < a.key_off[a.nmarkers]; ++k)
     if (a.key[k] < 0 || a.key[k] > 2147483647ll) return no(ARGS_RANGE, "key " + std::to_string(a.key[k]) + " does not fit int32");
   // marker sets
-  if (a.ms_off[0] != 0) return no(ARGS_INVALID, "ms_off does not start at 0");
-  for (uint32_t s = 0; s < a.nsets; ++s) {
-    if (a.ms_off[s + 1] < a.ms_off[s]) return no(ARGS_INVALID, "ms_off falls at marker set " + std::to_string(s));
-    if (a.ms_off[s + 1] > ncs) return no(ARGS_INVALID, "ms_off beyond the co-located sets at marker set " + std::to_string(s));
-    if (a.ms_off[s + 1] == a.ms_off[s]) return no(ARGS_INVALID, "marker set " + std::to_string(s) + " has no sets");
-  }
-  const uint64_t used_cs = a.ms_off[a.nsets];
-  if (used_cs > MAX_MEMBERS) return no(ARGS_RANGE, "more than 2^31 - 1 co-located sets");
-  if (a.cs_off[0] != 0) return no(ARGS_INVALID, "cs_off does not start at 0");
-  for (uint64_t c = 0; c < used_cs; ++c) {
-    if (a.cs_off[c + 1] < a.cs_off[c]) return no(ARGS_INVALID, "cs_off falls at co-located set " + std::to_string(c));
-    if (a.cs_off[c + 1] > nmembers) return no(ARGS_INVALID, "cs_off beyond the members at co-located set " + std::to_string(c));
-    if (a.cs_off[c + 1] == a.cs_off[c]) return no(ARGS_INVALID, "co-located set " + std::to_string(c) + " is empty");
-  }
-  const uint64_t used_members = a.cs_off[used_cs];
-  if (used_members > MAX_MEMBERS) return no(ARGS_RANGE, "more than 2^31 - 1 members of co-located sets");
-  if (used_members && !a.cs_marker) return no(ARGS_INVALID, "NULL members");
-  for (uint64_t e = 0; e < used_members; ++e)
-    if (a.cs_marker[e] >= a.nmarkers) return no(ARGS_INVALID, "marker index " + std::to_string(a.cs_marker[e]) + " beyond the keys");
+  if (const int kind = check_marker_sets(a.nmarkers, a.nsets, a.ms_off, a.cs_off, a.cs_marker, ncs, nmembers, why)) return kind;
   // replicates
   if (a.rs_off[0] != 0) return no(ARGS_INVALID, "rs_off does not start at 0");
   uint64_t max_starts = 0;

@@ -1,7 +1,8 @@
 """IMG, the reader of per-genome annotation tables, with the results of checkm/util/img.py for the methods MarkerSetBuilder needs:
 geneCountTable (:254-287), filterGeneCountTable (:289-309), familyIdToGeneId (:383-395), _genomeSeqLens (:397-406),
-_genomeFamilyPositions (:420-490), the two precompute methods (:408-418, :492-499), geneDistTable (:501-530) and the two redundancy
-filters (:555-589).  Plain host code.
+_genomeFamilyPositions (:420-490), the two precompute methods (:408-418, :492-499), geneDistTable (:501-530), the two redundancy
+filters (:555-589), and for the scaffold simulation filterGenomeIds (:42-48), geneIdToScaffoldId (:50-65), _genomeIdToClusterScaffold
+(:311-370) and precomputeGenomeFamilyScaffolds (:372-381).  Plain host code.
 
 A genome <id> is a directory <genomeDir>/<id>/ with <id>.pfam.tab.txt (family in column 8), <id>.tigrfam.tab.txt (family in column
 6), <id>.gff and <id>.fna.  As in the reference: the first line of an annotation table is a header; a column is taken as it stands
@@ -35,6 +36,45 @@ class IMG(object):
 
     def _path(self, genomeId, suffix):
         return os.path.join(self.genomeDir, genomeId, genomeId + suffix)
+
+    def filterGenomeIds(self, genomeIds, metadata, fieldToFilterOn, valueToRetain):
+        return set(g for g in genomeIds if metadata[g][fieldToFilterOn] == valueToRetain)
+
+    # ---- scaffolds ------------------------------------------------------------------------------------------------------------------
+    def _gff_genes(self, genomeId):
+        """(scaffold id, gene id, fields) of every GFF record, by this module's GFF rule."""
+        with open(self._path(genomeId, '.gff')) as f:
+            for line in f:
+                if line[0] == '#':
+                    continue
+                fields = line.split('\t')
+                if len(fields) != 9:
+                    continue
+                tag = fields[8].split(';')[0]
+                yield fields[0], tag[tag.find('=') + 1:], fields
+
+    def geneIdToScaffoldId(self, genomeId):
+        """gene -> scaffold (:50-65).  The reference indexes field nine of every line and cuts the gene id at the first ';'; on records
+        of nine fields with a ';' the two rules agree, and a line of fewer fields is skipped here where the reference fails."""
+        return {geneId: scaffoldId for scaffoldId, geneId, _ in self._gff_genes(genomeId)}
+
+    def _genomeIdToClusterScaffold(self, genomeId):
+        """family -> [scaffold id, ...] of its genes that have a GFF record, one entry per gene (:311-370); a family none of whose
+        genes has a record is absent.  The copies follow the sorted gene ids.  The reference keeps a TIGRFAM by the record of the gene
+        its set of gene ids happens to yield last (:362 tests `scaffold`, not `scaffolds`), which is the Pfam rule whenever all genes of
+        the family or none have a record; the Pfam rule is applied to both tables here."""
+        where = self.geneIdToScaffoldId(genomeId)
+        out = {}
+        for extension, column in ((self.pfamExtension, 8), (self.tigrExtension, 6)):
+            for familyId, geneIds in self.familyIdToGeneId(self._path(genomeId, extension), column).items():
+                scaffolds = [where[g] for g in sorted(geneIds) if g in where]
+                if scaffolds:
+                    out[familyId] = scaffolds
+        return out
+
+    def precomputeGenomeFamilyScaffolds(self, genomeIds):
+        self.cachedGenomeFamilyScaffolds = {g: self._genomeIdToClusterScaffold(g) for g in genomeIds}
+        return self.cachedGenomeFamilyScaffolds
 
     # ---- counts ---------------------------------------------------------------------------------------------------------------------
     def _count_families(self, table, genomeIds, extension, column):
@@ -78,6 +118,7 @@ class IMG(object):
 
     # ---- positions ------------------------------------------------------------------------------------------------------------------
     def _genomeSeqLens(self, genomeId):
+        """sequence id -> length, in the order of the FASTA file: numpy's choice in the scaffold samplers sees list(seqLens.keys())."""
         return {seqId: len(seq) for seqId, seq in _read_fna(self._path(genomeId, '.fna')).items()}
 
     def precomputeGenomeSeqLens(self, genomeIds):

@@ -14,8 +14,13 @@ sorted, colocatedSets its sets sorted by their smallest member.  Equality with t
 
 The simulation methods of the script (:265-369) are here as plain Python with the reference's results -- uniformity, sampleGenome,
 sampleGenomeScaffoldsInvLength, sampleGenomeScaffoldsWithoutReplacement, containedMarkerGenes -- and genomeChecks scores every marker set
-on every draw of a genome with one device call (kernels_sim.hip).  markerGenesOnScaffolds and the tree-walking
-methods (buildBinMarkerSet, ...) are not here."""
+on every draw of a genome with one device call (kernels_sim.hip).
+
+The scaffold simulation: markerGenesOnScaffolds (:371-378) is the reference's plain loop, scaffoldChecks scores every
+marker set on every draw of scaffolds of a test genome and a contaminant with one device call (kernels_simscaf.hip).  The tree walk
+(buildBinMarkerSet :587-634, buildDomainMarkerSet :636-687) runs over checkm_amd.treeParser's tree; its three data files are read by
+readNodeMetadata, readDuplicateSeqs and readLineageSpecificGenesToRemove from paths the caller gives, or assigned as dicts.
+buildBinMarkerSetsLOO answers the leave-one-out chains of many genomes from ONE buildMarkerSets call."""
 from collections import defaultdict
 import logging
 import random
@@ -23,7 +28,7 @@ import time
 
 import numpy as np
 
-from checkm_amd.markerSets import MarkerSet
+from checkm_amd.markerSets import BinMarkerSets, MarkerSet
 
 
 def _pair_name(a, b):
@@ -105,6 +110,13 @@ class MarkerSetBuilder(object):
         self.cachedGeneCountTable = None
         self.last_timing = {}
         self.last_sim_timing = {}
+        self.last_scaffold_timing = {}
+        self.duplicateSeqs = {}                      # leaf label -> labels of the genomes dereplicated into it
+        self.uniqueIdToLineageStatistics = {}        # node uid -> statistics of the node
+        self.lineageSpecificGenesToRemove = {}       # node uid -> genes lost or duplicated in that lineage
+
+    def precomputeGenomeFamilyScaffolds(self, genomeIds):
+        self.img.precomputeGenomeFamilyScaffolds(genomeIds)
 
     def precomputeGenomeSeqLens(self, genomeIds):
         self.img.precomputeGenomeSeqLens(genomeIds)
@@ -462,3 +474,208 @@ class MarkerSetBuilder(object):
         r = _lib.sim_run(self._ctx(), tables)
         t.update(pack=t['pack'] + r['ms_pack'] / 1e3, copy_in=r['ms_upload'] / 1e3, kernel=r['ms_kernel'] / 1e3, copy_out=r['ms_download'] / 1e3, rounds=r['nrounds'], device=True)
         return r['out']
+
+    # ---- the scaffold simulation (markerSetBuilder.py:371-378) -----------------------------------------------------------
+    def markerGenesOnScaffolds(self, markerGenes, genomeId, scaffoldIds, containedMarkerGenes):
+        """Appends to containedMarkerGenes[marker] the scaffold of every copy of the marker in genomeId that lies on one of scaffoldIds.
+        The plain loop: what scaffoldChecks runs in place of the device for a call the library refuses, and what it is tested against."""
+        scaffoldsOf = self.img.cachedGenomeFamilyScaffolds[genomeId]
+        for markerGeneId in markerGenes:
+            for scaffoldId in scaffoldsOf.get(markerGeneId, []):
+                if scaffoldId in scaffoldIds:
+                    containedMarkerGenes[markerGeneId] += [scaffoldId]
+
+    def _scaffold_checks_host(self, markerSets, testGenomeId, draws):
+        out = np.zeros((len(draws), len(markerSets), 4), dtype=np.float64)
+        for r, (retainedTestSeqIds, contGenomeId, contSampledSeqIds) in enumerate(draws):
+            for s, ms in enumerate(markerSets):
+                contained = defaultdict(list)
+                self.markerGenesOnScaffolds(ms.getMarkerGenes(), testGenomeId, retainedTestSeqIds, contained)
+                if contGenomeId is not None:
+                    self.markerGenesOnScaffolds(ms.getMarkerGenes(), contGenomeId, contSampledSeqIds, contained)
+                out[r, s] = self._genome_check_host(ms, contained)
+        return out
+
+    def _scaffold_tables(self, markerSets, testGenomeId, draws):
+        """The arrays of one ckm_simscaf_run call (include/checkm_hip.h): genome 0 is the test genome, the contaminants follow sorted;
+        the distinct markers of all sets sorted by name; a genome's scaffolds are those that carry a copy of one of these markers,
+        numbered as the copies meet them -- an id only the FASTA file knows has no copy and needs no bit, an id only the GFF file knows
+        has a bit that no draw sets."""
+        from checkm_amd import _lib
+        cached = self.img.cachedGenomeFamilyScaffolds
+        genomes = [testGenomeId] + sorted(set(d[1] for d in draws if d[1] is not None) - set([testGenomeId]))
+        gidx = {g: k for k, g in enumerate(genomes)}
+        markers = sorted(set(m for ms in markerSets for m in ms.getMarkerGenes()))
+        midx = {m: k for k, m in enumerate(markers)}
+        index, sc, lens = [], [], []
+        for g in genomes:
+            ids = {}
+            for m in markers:
+                copies = cached[g].get(m, [])
+                sc.extend(ids.setdefault(s, len(ids)) for s in copies)
+                lens.append(len(copies))
+            index.append(ids)
+        off = lambda n: np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(n, dtype=np.uint64)])
+        words = [(len(ids) + 31) // 32 for ids in index]
+        test, cont, rows, row_lens = [], [], [], []
+
+        def row(g, seqIds):
+            ids = index[g]
+            at = np.fromiter((ids[s] for s in seqIds if s in ids), dtype=np.int64)
+            w = np.zeros(words[g], dtype=np.uint32)
+            np.bitwise_or.at(w, at >> 5, (np.uint32(1) << (at & 31).astype(np.uint32)))
+            return w
+
+        for retainedTestSeqIds, contGenomeId, contSampledSeqIds in draws:
+            test.append(0)
+            rows.append(row(0, retainedTestSeqIds))
+            n = words[0]
+            if contGenomeId is None:
+                cont.append(_lib.SIMSCAF_NONE)
+            else:
+                cont.append(gidx[contGenomeId])
+                rows.append(row(gidx[contGenomeId], contSampledSeqIds))
+                n += words[gidx[contGenomeId]]
+            row_lens.append(n)
+        sets = [list(cs) for ms in markerSets for cs in ms.markerSet]
+        return _lib.SimScafTables([len(ids) for ids in index], len(markers), off(lens), sc, off([len(ms.markerSet) for ms in markerSets]), off([len(cs) for cs in sets]),
+                                  [midx[m] for cs in sets for m in cs], test, cont, off(row_lens), np.concatenate(rows) if rows else [])
+
+    def scaffoldChecks(self, markerSets, testGenomeId, draws):
+        """out[replicate][markerSet] = (individual completeness, individual contamination, set completeness, set contamination): for
+        every draw (retainedTestSeqIds, contGenomeId or None, contSampledSeqIds) and marker set what markerGenesOnScaffolds over the
+        test genome and over the contaminant followed by MarkerSet.genomeCheck in both modes gives, from ONE device call.  The scaffolds
+        of the markers come from precomputeGenomeFamilyScaffolds.  A call the library refuses (a marker set without sets -- the
+        reference's ZeroDivisionError) runs the plain loop."""
+        markerSets, draws = list(markerSets), [tuple(d) for d in draws]
+        t = dict(pack=0.0, copy_in=0.0, kernel=0.0, copy_out=0.0, rounds=0, device=False)
+        self.last_scaffold_timing = t
+        from checkm_amd import _lib
+        t0 = time.perf_counter()
+        tables = self._scaffold_tables(markerSets, testGenomeId, draws)
+        try:
+            _lib.simscaf_check(tables)
+        except _lib.CkmError:
+            tables = None
+        t['pack'] = time.perf_counter() - t0
+        if tables is None:
+            return self._scaffold_checks_host(markerSets, testGenomeId, draws)
+        r = _lib.simscaf_run(self._ctx(), tables)
+        t.update(pack=t['pack'] + r['ms_pack'] / 1e3, copy_in=r['ms_upload'] / 1e3, kernel=r['ms_kernel'] / 1e3, copy_out=r['ms_download'] / 1e3, rounds=r['nrounds'], device=True)
+        return r['out']
+
+    # ---- the tree walk (markerSetBuilder.py:380-484, :576-687) --------------------------------------------------------------------------------
+    def readDuplicateSeqs(self, path):
+        """leaf label -> labels of the genomes whose alignments repeat it (the derep list: a label and its duplicates per line)."""
+        self.duplicateSeqs = {}
+        with open(path) as f:
+            for line in f:
+                fields = line.rstrip().split()
+                if len(fields) > 1:
+                    self.duplicateSeqs[fields[0]] = fields[1:]
+        return self.duplicateSeqs
+
+    def readNodeMetadata(self, path):
+        """node uid -> statistics of the node (the node metadata table; the walk reads 'taxonomy')."""
+        stats = {}
+        with open(path) as f:
+            f.readline()
+            for line in f:
+                fields = line.rstrip().split('\t')
+                d = {'# genomes': int(fields[1]), 'taxonomy': fields[2]}
+                try:
+                    d['bootstrap'] = float(fields[3])
+                except ValueError:
+                    d['bootstrap'] = 'NA'
+                d['gc mean'], d['gc std'] = float(fields[4]), float(fields[5])
+                d['genome size mean'], d['genome size std'] = float(fields[6]) / 1e6, float(fields[7]) / 1e6
+                d['gene count mean'], d['gene count std'] = float(fields[8]), float(fields[9])
+                d['marker set'] = fields[10].rstrip()
+                stats[fields[0]] = d
+        self.uniqueIdToLineageStatistics = stats
+        return stats
+
+    def readLineageSpecificGenesToRemove(self, path):
+        """node uid -> genes lost or duplicated in that lineage (uid, set literal of the missing, set literal of the duplicated)."""
+        from checkm_amd.treeParser import parse_set_literal
+        self.lineageSpecificGenesToRemove = {}
+        with open(path) as f:
+            for line in f:
+                fields = line.rstrip('\n').split('\t')
+                self.lineageSpecificGenesToRemove[fields[0]] = parse_set_literal(fields[1]) | parse_set_literal(fields[2])
+        return self.lineageSpecificGenesToRemove
+
+    def _next_named_node(self, node):
+        """Taxonomy of the first labelled ancestor that has one, else 'root' (:421-436)."""
+        p = node.parent
+        while p is not None:
+            if p.label:
+                taxonomy = self.uniqueIdToLineageStatistics[p.label.split('|')[0]]['taxonomy']
+                if taxonomy != '':
+                    return taxonomy
+            p = p.parent
+        return 'root'
+
+    @staticmethod
+    def _without(markerSet, genesToRemove):
+        """The marker set without those genes; a co-located set left empty is dropped (:461-484)."""
+        kept = [cs - genesToRemove for cs in markerSet.markerSet]
+        return MarkerSet(markerSet.UID, markerSet.lineageStr, markerSet.numGenomes, [cs for cs in kept if cs])
+
+    def _chain_nodes(self, curNode, genomeIdsToRemove, domainOnly):
+        """[(lineageStr, sorted genome ids)] of the nodes from curNode to the root that keep at least two genomes (:598-632): the leaves
+        below the node and the genomes dereplicated into them, without genomeIdsToRemove."""
+        out = []
+        removed = set(genomeIdsToRemove) if genomeIdsToRemove is not None else set()
+        while curNode is not None:
+            uniqueId = curNode.label.split('|')[0]
+            if not domainOnly or uniqueId in ('UID2', 'UID203'):
+                taxonomyStr = self.uniqueIdToLineageStatistics[uniqueId]['taxonomy']
+                if taxonomyStr == '':
+                    taxonomyStr = self._next_named_node(curNode)
+                genomeIds = set()
+                for leaf in curNode.leaves():
+                    genomeIds.add(leaf.taxon.replace('IMG_', ''))
+                    genomeIds.update(dup.replace('IMG_', '') for dup in self.duplicateSeqs.get(leaf.taxon, []))
+                genomeIds -= removed
+                if len(genomeIds) >= 2:
+                    out.append((uniqueId + ' | ' + taxonomyStr.split(';')[-1], sorted(genomeIds)))
+            curNode = curNode.parent
+        return out
+
+    def _chains(self, starts, ubiquityThreshold, singleCopyThreshold, bMarkerSet, domainOnly=False):
+        """[(binMarkerSets, refinedBinMarkerSet)] for every (node, genomeIdsToRemove) of starts.  The genome lists of all chains, each
+        distinct list once, are answered by one buildMarkerSets call (bMarkerSet) or by buildMarkerGenes per list."""
+        chains = [self._chain_nodes(node, remove, domainOnly) for node, remove in starts]
+        lists = sorted(set(tuple(ids) for chain in chains for _, ids in chain))
+        if bMarkerSet:
+            built = self.buildMarkerSets([list(ids) for ids in lists], ubiquityThreshold, singleCopyThreshold) if lists else []
+            sets = {ids: ms.markerSet for ids, ms in zip(lists, built)}
+        else:
+            sets = {ids: [self.buildMarkerGenes(list(ids), ubiquityThreshold, singleCopyThreshold)] for ids in lists}
+        out = []
+        for (node, _), chain in zip(starts, chains):
+            refinement = self.lineageSpecificGenesToRemove[node.label.split('|')[0]]
+            binMarkerSets, refined = BinMarkerSets(node.label, BinMarkerSets.TREE_MARKER_SET), BinMarkerSets(node.label, BinMarkerSets.TREE_MARKER_SET)
+            for lineageStr, ids in chain:
+                markerSet = MarkerSet(0, lineageStr, len(ids), [set(cs) for cs in sets[tuple(ids)]])
+                binMarkerSets.addMarkerSet(markerSet)
+                refined.addMarkerSet(self._without(markerSet, refinement))
+            out.append((binMarkerSets, refined))
+        return out
+
+    def buildBinMarkerSet(self, tree, curNode, ubiquityThreshold, singleCopyThreshold, bMarkerSet=True, genomeIdsToRemove=None):
+        """(binMarkerSets, refinedBinMarkerSet): the marker sets of every node from curNode to the root that keeps at least two genomes
+        once genomeIdsToRemove are taken out, and the same without the genes lost or duplicated in curNode's lineage (:587-634)."""
+        return self._chains([(curNode, genomeIdsToRemove)], ubiquityThreshold, singleCopyThreshold, bMarkerSet)[0]
+
+    def buildDomainMarkerSet(self, tree, curNode, ubiquityThreshold, singleCopyThreshold, bMarkerSet=True, genomeIdsToRemove=None):
+        """buildBinMarkerSet over the bacterial and archaeal nodes (UID2, UID203) alone (:636-687)."""
+        return self._chains([(curNode, genomeIdsToRemove)], ubiquityThreshold, singleCopyThreshold, bMarkerSet, domainOnly=True)[0]
+
+    def buildBinMarkerSetsLOO(self, tree, testGenomeIds, ubiquityThreshold, singleCopyThreshold, bMarkerSet=True):
+        """genomeId -> buildBinMarkerSet(tree, parent of the leaf 'IMG_' + genomeId, ..., genomeIdsToRemove=[genomeId]), with the genome
+        lists of every (genome, ancestor) pair answered by ONE buildMarkerSets call on the resident table."""
+        testGenomeIds = list(testGenomeIds)
+        starts = [(tree.find_leaf('IMG_' + g).parent, [g]) for g in testGenomeIds]
+        return dict(zip(testGenomeIds, self._chains(starts, ubiquityThreshold, singleCopyThreshold, bMarkerSet)))

@@ -5,8 +5,8 @@ contig lengths, completeness and contamination levels (worker :97-145), and the 
 The reference scores every marker set on every draw with containedMarkerGenes and MarkerSet.genomeCheck, markers x copies x contigs
 Python iterations each.  Here all draws of a genome are made on the host, in the reference's order, so that a seeded caller gets its
 contigs, and go to ONE MarkerSetBuilder.genomeChecks call (kernels_sim.hip).  The marker sets are the caller's: this
-package's BinMarkerSets and MarkerSet.  The tree walk that builds them in the reference (buildBinMarkerSet, dendropy, its authors'
-metadata files) is not here; neither are the process pool and the queues, which the single device call replaces."""
+package's BinMarkerSets and MarkerSet, for instance from MarkerSetBuilder.buildBinMarkerSet.  The process pool and the queues are
+replaced by the single device call."""
 from collections import defaultdict
 import gzip
 import time

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_place_* and ckm_nhmm_* */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_* and ckm_nhmm_* */
 
 enum {
   CKM_OK      =  0,
@@ -792,6 +792,44 @@ typedef struct {
 } ckm_sim_info;
 int  ckm_sim_check(const ckm_sim_args *a);
 int  ckm_sim_run(ckm_ctx *ctx, const ckm_sim_args *a, uint64_t budget_bytes, double *out, ckm_sim_info *info);
+
+/* ---- SimulationScaffolds: marker sets scored on genomes sampled by scaffold (additions to ABI 12) ----------------------------
+ * Replaces the loop nest of the workers of scripts/simulationScaffoldsRandom.py and scripts/simulationScaffoldsByLength.py (:137-162): per
+ * draw MarkerSetBuilder.markerGenesOnScaffolds (scripts/genometreeworkflow/markerSetBuilder.py:371-378) for the test genome and for the
+ * contaminant, and both modes of MarkerSet.genomeCheck (checkm/markerSets.py:206-238) for every marker set.
+ * checkm_amd/csrc/simscaf_dev.h, kernels_simscaf.hip.
+ *
+ * Resident: ngenomes genomes with nscaf[g] scaffolds each, and for the nmarkers distinct markers of all marker sets of the call the cells
+ * (g, m) = g * nmarkers + m: sc[sc_off[cell] .. sc_off[cell + 1] - 1] are the scaffold indices (< nscaf[g]) of the copies of marker m in
+ * genome g, one entry per copy (nsc entries in all).  The marker sets are ckm_sim_args' ms_off / cs_off / cs_marker.
+ * Replicates: replicate r has the test genome test[r], the contaminant cont[r] (CKM_SIMSCAF_NONE: none; it may equal test[r]) and the words
+ * bits[bit_off[r] .. bit_off[r + 1] - 1]: (nscaf[test[r]] + 31) / 32 words, bit i % 32 of word i / 32 set where scaffold i of the test genome
+ * is kept, then (nscaf[cont[r]] + 31) / 32 words for the scaffolds of the contaminant that are sampled in (nwords words in all).
+ * Every offset table starts at 0 and never falls.
+ *
+ * A marker's count is the number of its copies in the test genome on a kept scaffold plus the number of its copies in the contaminant on a
+ * sampled scaffold.  out holds four float64 per (replicate, marker set), out[(r * nsets + s) * 4 ..], as ckm_sim_run's.
+ * One launch covers the replicates of a round; a call goes in rounds of whole replicates within budget_bytes (0: CKM_SIMSCAF_BATCH_MB,
+ * default 256, << 20; a round holds at least one replicate), which never changes a result.  info may be NULL.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, an offset table that does not start at 0, falls or points beyond its table,
+ * a scaffold index >= nscaf[g], a genome index >= ngenomes, a marker index >= nmarkers, bit rows whose length is not that of the two genomes,
+ * a bit set at or beyond nscaf, a co-located set without a member, a marker set without a co-located set; CKM_ERANGE for more than 2^24
+ * genomes, markers or replicates, more than 2^20 marker sets, more than 2^28 cells, more than 2^30 scaffolds in a genome, more than
+ * 2^31 - 1 copies, or a cell with 2^30 copies or more (a marker's copies in two genomes stay below 2^31).  ckm_simscaf_check applies the
+ * same tests and needs no device: the caller then computes such a call with its own loop. */
+#define CKM_SIMSCAF_NONE 0xffffffffu
+typedef struct {
+  uint32_t        ngenomes;    const uint32_t *nscaf;
+  uint32_t        nmarkers;    const uint64_t *sc_off;   const uint32_t *sc;        uint64_t nsc;
+  uint32_t        nsets;       const uint64_t *ms_off;   const uint64_t *cs_off;    uint64_t ncs;
+  const uint32_t *cs_marker;   uint64_t        nmembers;
+  uint32_t        nreplicates; const uint32_t *test;     const uint32_t *cont;
+  const uint64_t *bit_off;     const uint32_t *bits;     uint64_t        nwords;
+} ckm_simscaf_args;
+typedef ckm_sim_info ckm_simscaf_info;
+int  ckm_simscaf_check(const ckm_simscaf_args *a);
+int  ckm_simscaf_run(ckm_ctx *ctx, const ckm_simscaf_args *a, uint64_t budget_bytes, double *out, ckm_simscaf_info *info);
 
 /* ---- PplacerRunner: bins placed on the edges of the reference tree (additions to ABI 12) -------------------------------------
  * Replaces the pplacer call of checkm/pplacer.py:70-80 by a grid search on the device.  checkm_amd/csrc/place_dev.h, kernels_place.hip.
