@@ -209,6 +209,17 @@ class SimScafArgs(C.Structure):
                 ("nreplicates", C.c_uint32), ("test", C.c_void_p), ("cont", C.c_void_p), ("bit_off", C.c_void_p), ("bits", C.c_void_p), ("nwords", C.c_uint64)]
 
 
+class SelectArgs(C.Structure):
+    _fields_ = [("ngenomes", C.c_uint32), ("genome_len", C.c_void_p), ("nmarkers", C.c_uint32), ("key_off", C.c_void_p), ("key", C.c_void_p), ("nkeys", C.c_uint64),
+                ("nsets", C.c_uint32), ("ms_off", C.c_void_p), ("cs_off", C.c_void_p), ("ncs", C.c_uint64), ("cs_marker", C.c_void_p), ("nmembers", C.c_uint64),
+                ("nreplicates", C.c_uint32), ("contig_len", C.c_int64), ("comp_lo", C.c_double), ("comp_hi", C.c_double), ("cont_lo", C.c_double), ("cont_hi", C.c_double),
+                ("seed", C.c_uint64)]
+
+
+class SelectOut(C.Structure):
+    _fields_ = [("truth", C.c_void_p), ("out", C.c_void_p), ("rows", C.c_void_p)]
+
+
 class PlaceArgs(C.Structure):
     _fields_ = [("nnodes", C.c_uint32), ("child_off", C.c_void_p), ("child", C.c_void_p), ("nchild", C.c_uint64), ("length", C.c_void_p),
                 ("nsites", C.c_uint32), ("nrows", C.c_uint32), ("row_off", C.c_void_p), ("rows", C.c_void_p), ("nrow_bytes", C.c_uint64),
@@ -287,7 +298,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_fasta_ids_read", "ckm_fasta_ids_view_get", "ckm_fasta_ids_free", "ckm_unbinned_select", "ckm_unbinned_count", "ckm_unbinned_write",
            "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
-           "ckm_sim_check", "ckm_sim_run", "ckm_simscaf_check", "ckm_simscaf_run", "ckm_place_check", "ckm_place_run",
+           "ckm_sim_check", "ckm_sim_run", "ckm_simscaf_check", "ckm_simscaf_run", "ckm_select_check", "ckm_select_run", "ckm_place_check", "ckm_place_run",
            "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
@@ -425,6 +436,8 @@ def load():
     L.ckm_sim_run.argtypes = [C.c_void_p, C.POINTER(SimArgs), C.c_uint64, C.c_void_p, C.POINTER(SimInfo)]
     L.ckm_simscaf_check.argtypes = [C.POINTER(SimScafArgs)]
     L.ckm_simscaf_run.argtypes = [C.c_void_p, C.POINTER(SimScafArgs), C.c_uint64, C.c_void_p, C.POINTER(SimInfo)]
+    L.ckm_select_check.argtypes = [C.POINTER(SelectArgs)]
+    L.ckm_select_run.argtypes = [C.c_void_p, C.POINTER(SelectArgs), C.c_uint64, C.POINTER(SelectOut), C.POINTER(SimInfo)]
     L.ckm_place_check.argtypes = [C.POINTER(PlaceArgs)]
     L.ckm_place_run.argtypes = [C.c_void_p, C.POINTER(PlaceArgs), C.c_uint64, C.POINTER(PlaceOut), C.POINTER(PlaceInfo)]
     L.ckm_nhmm_check.argtypes = [C.POINTER(NhmmArgs)]
@@ -1653,6 +1666,72 @@ def simscaf_run(ctx, tables, budget_bytes=0):
     info, a = SimInfo(), tables.args()
     _chk(load().ckm_simscaf_run(ctx.h, C.byref(a), int(budget_bytes), _ptr(out), C.byref(info)))
     return dict(out=out, nrounds=int(info.nrounds), **{f: getattr(info, f) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")})
+
+
+class SelectTables(object):
+    """The arrays of one selection call as ckm_select_check / ckm_select_run take them (include/checkm_hip.h): genome_len per test genome,
+    key_off / key for the (genome, marker) cells, ms_off / cs_off / cs_marker for the marker sets, the replicates per genome, the contig
+    length, the two ranges and the seed.  Keys and lengths are int64 here; the library checks them down to int32."""
+
+    def __init__(self, genome_len, nmarkers, key_off, key, ms_off, cs_off, cs_marker, nreplicates, contig_len, comp_range, cont_range, seed):
+        u64 = lambda x: np.ascontiguousarray(x, dtype=np.uint64).reshape(-1)
+        i64 = lambda x: np.ascontiguousarray(x, dtype=np.int64).reshape(-1)
+        self.genome_len, self.key_off, self.key, self.ms_off, self.cs_off = i64(genome_len), u64(key_off), i64(key), u64(ms_off), u64(cs_off)
+        self.cs_marker = np.ascontiguousarray(cs_marker, dtype=np.uint32).reshape(-1)
+        self.ngenomes, self.nmarkers, self.nreplicates, self.contig_len = self.genome_len.shape[0], int(nmarkers), int(nreplicates), int(contig_len)
+        if not (self.ms_off.size and self.cs_off.size):
+            raise ValueError("an offset table holds at least its leading 0")
+        if self.key_off.shape[0] != self.ngenomes * self.nmarkers + 1:
+            raise ValueError("one offset per (genome, marker) cell and the end")
+        self.nsets = self.ms_off.shape[0] - 1
+        (self.comp_lo, self.comp_hi), (self.cont_lo, self.cont_hi) = (float(x) for x in comp_range), (float(x) for x in cont_range)
+        self.seed = int(seed) & 0xffffffffffffffff
+
+    def args(self):
+        """The ckm_select_args of these arrays (it borrows them: keep this object alive over the call)."""
+        return SelectArgs(self.ngenomes, _ptr(self.genome_len), self.nmarkers, self.key_off.ctypes.data, _ptr(self.key), self.key.shape[0],
+                          self.nsets, self.ms_off.ctypes.data, self.cs_off.ctypes.data, self.cs_off.shape[0] - 1, _ptr(self.cs_marker), self.cs_marker.shape[0],
+                          self.nreplicates, self.contig_len, self.comp_lo, self.comp_hi, self.cont_lo, self.cont_hi, self.seed)
+
+    def ncontigs(self):
+        """C_g of every genome (of a call that passed select_check)."""
+        return [int(n) // self.contig_len for n in self.genome_len]
+
+
+def select_check(tables):
+    """ckm_select_check: why the genomes, the keys, the marker sets or the ranges of a call would be refused, without a device.  Raises
+    CkmError as select_run would."""
+    a = tables.args()
+    _chk(load().ckm_select_check(C.byref(a)))
+
+
+def select_arrays(tables, with_rows):
+    """The result arrays of a call: truth [G, R, 2], out [G, R, S, 4] and, on request, the flat uint16 multiplicity rows."""
+    truth = np.zeros((tables.ngenomes, tables.nreplicates, 2), dtype=np.float64)
+    out = np.zeros((tables.ngenomes, tables.nreplicates, tables.nsets, 4), dtype=np.float64)
+    rows = np.zeros(sum(tables.ncontigs()) * tables.nreplicates, dtype=np.uint16) if with_rows else None
+    return truth, out, rows
+
+
+def select_rows(tables, rows):
+    """The flat multiplicity rows as one array [R, C_g] per genome."""
+    split, at = [], 0
+    for c in tables.ncontigs():
+        split.append(rows[at:at + tables.nreplicates * c].reshape(tables.nreplicates, c))
+        at += tables.nreplicates * c
+    return split
+
+
+def select_run(ctx, tables, budget_bytes=0, with_rows=False):
+    """The selection pass (ckm_select_run) over all draws of a call.  Returns a dict: truth [ngenomes, nreplicates, 2] float64 (true
+    completeness and contamination of every draw, in percent), out [ngenomes, nreplicates, nsets, 4] float64 as sim_run's, rows (with_rows:
+    per genome the uint16 multiplicities [nreplicates, C_g], else None), nrounds and the timings in ms."""
+    info, a = SimInfo(), tables.args()
+    truth, out, rows = select_arrays(tables, with_rows)
+    o = SelectOut(_ptr(truth), _ptr(out), _ptr(rows) if with_rows else None)
+    _chk(load().ckm_select_run(ctx.h, C.byref(a), int(budget_bytes), C.byref(o), C.byref(info)))
+    return dict(truth=truth, out=out, rows=select_rows(tables, rows) if with_rows else None, nrounds=int(info.nrounds),
+                **{f: getattr(info, f) for f in ("ms_pack", "ms_upload", "ms_kernel", "ms_download", "ms_total")})
 
 
 class PlaceTables(object):

@@ -111,6 +111,7 @@ class MarkerSetBuilder(object):
         self.last_timing = {}
         self.last_sim_timing = {}
         self.last_scaffold_timing = {}
+        self.last_select_timing = {}
         self.duplicateSeqs = {}                      # leaf label -> labels of the genomes dereplicated into it
         self.uniqueIdToLineageStatistics = {}        # node uid -> statistics of the node
         self.lineageSpecificGenesToRemove = {}       # node uid -> genes lost or duplicated in that lineage
@@ -474,6 +475,70 @@ class MarkerSetBuilder(object):
         r = _lib.sim_run(self._ctx(), tables)
         t.update(pack=t['pack'] + r['ms_pack'] / 1e3, copy_in=r['ms_upload'] / 1e3, kernel=r['ms_kernel'] / 1e3, copy_out=r['ms_download'] / 1e3, rounds=r['nrounds'], device=True)
         return r['out']
+
+    # ---- sampled genomes drawn on the device (scripts/simInferBestMarkerSet.py:94-110) ------------------------------------
+    @staticmethod
+    def _select_tables(markerSets, genePositionsPerGenome, genomeSizes, numReplicates, contigLen, compRange, contRange, seed):
+        """The arrays of one ckm_select_run call (include/checkm_hip.h), or None where they cannot be said in its number types: the
+        distinct markers of all sets sorted by name, their copies' starts per test genome, the marker sets as lists of co-located sets."""
+        from checkm_amd import _lib
+        markers = sorted(set(m for ms in markerSets for m in ms.getMarkerGenes()))
+        midx = {m: k for k, m in enumerate(markers)}
+        copies = [[p[0] for p in positions.get(m, [])] for positions in genePositionsPerGenome for m in markers]
+        flat = [x for c in copies for x in c] + list(genomeSizes) + [contigLen, numReplicates]
+        if not isinstance(seed, (int, np.integer)) or not all(isinstance(x, (int, np.integer)) and not isinstance(x, bool) and -(1 << 63) <= x < (1 << 63) for x in flat):
+            return None
+        if not 0 <= numReplicates < (1 << 32) or not all(isinstance(x, (int, float)) for x in tuple(compRange) + tuple(contRange)):
+            return None
+        off = lambda lens: np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(lens, dtype=np.uint64)])
+        sets = [list(cs) for ms in markerSets for cs in ms.markerSet]
+        return _lib.SelectTables(list(genomeSizes), len(markers), off([len(c) for c in copies]), [x for c in copies for x in c], off([len(ms.markerSet) for ms in markerSets]),
+                                 off([len(cs) for cs in sets]), [midx[m] for cs in sets for m in cs], numReplicates, contigLen, compRange, contRange, seed)
+
+    def _sampled_checks_host(self, markerSets, genePositionsPerGenome, genomeSizes, numReplicates, contigLen, compRange, contRange, seed):
+        """The same draws in plain Python (checkm_amd.selectDraws), scored by the plain loop of genomeChecks."""
+        from checkm_amd import selectDraws
+        true = np.zeros((len(genomeSizes), numReplicates, 2), dtype=np.float64)
+        out = np.zeros((len(genomeSizes), numReplicates, len(markerSets), 4), dtype=np.float64)
+        mults = []
+        for g, (positions, genomeSize) in enumerate(zip(genePositionsPerGenome, genomeSizes)):
+            rows = np.zeros((numReplicates, max(genomeSize // contigLen, 0)), dtype=np.uint16)
+            for r in range(numReplicates):
+                true[g, r, 0], true[g, r, 1], mult = selectDraws.draw(seed, g, r, genomeSize, contigLen, compRange, contRange)
+                rows[r] = np.minimum(mult, 65535)
+                out[g, r] = self._genome_checks_host(markerSets, positions, [selectDraws.contig_starts(mult, contigLen)], [contigLen])[0]
+            mults.append(rows)
+        return true, out, mults
+
+    def sampledGenomeChecks(self, markerSets, genePositionsPerGenome, genomeSizes, numReplicates, contigLen, compRange=(0.5, 1.0), contRange=(0.0, 0.2), seed=0,
+                            withDraws=False):
+        """(true[genome][replicate] = (true completeness, true contamination), out[genome][replicate][markerSet] = genomeChecks' four
+        values) for numReplicates draws of sampleGenome per test genome, the target fractions uniform in compRange and contRange -- the
+        replicate loop of scripts/simInferBestMarkerSet.py (:94-110) from ONE device call.  The draws are made on the device from a
+        counter-based generator (Philox4x32-10 keyed by seed), so they are a function of the arguments alone and are not Python's.
+        genePositionsPerGenome[g] is geneDistTable[genomeId] of test genome g.  withDraws: also, per genome, how often every contig was
+        drawn, uint16 [replicate][contig], as the library returns it: min(multiplicity, 65535).  A call the library refuses (more contigs
+        than a block keeps, a position beyond int32, ...) makes the same draws in plain Python and scores them with the plain loop."""
+        markerSets, genePositionsPerGenome, genomeSizes = list(markerSets), list(genePositionsPerGenome), list(genomeSizes)
+        if len(genePositionsPerGenome) != len(genomeSizes):
+            raise ValueError('one genome size per test genome')
+        t = dict(pack=0.0, copy_in=0.0, kernel=0.0, copy_out=0.0, rounds=0, device=False)
+        self.last_select_timing = t
+        from checkm_amd import _lib
+        t0 = time.perf_counter()
+        tables = self._select_tables(markerSets, genePositionsPerGenome, genomeSizes, numReplicates, contigLen, compRange, contRange, seed)
+        if tables is not None:
+            try:
+                _lib.select_check(tables)
+            except _lib.CkmError:
+                tables = None
+        t['pack'] = time.perf_counter() - t0
+        if tables is None:
+            true, out, mults = self._sampled_checks_host(markerSets, genePositionsPerGenome, genomeSizes, numReplicates, contigLen, compRange, contRange, seed)
+            return (true, out, mults) if withDraws else (true, out)
+        r = _lib.select_run(self._ctx(), tables, with_rows=withDraws)
+        t.update(pack=t['pack'] + r['ms_pack'] / 1e3, copy_in=r['ms_upload'] / 1e3, kernel=r['ms_kernel'] / 1e3, copy_out=r['ms_download'] / 1e3, rounds=r['nrounds'], device=True)
+        return (r['truth'], r['out'], r['rows']) if withDraws else (r['truth'], r['out'])
 
     # ---- the scaffold simulation (markerSetBuilder.py:371-378; DESIGN section 25) -----------------------------------------------------------
     def markerGenesOnScaffolds(self, markerGenes, genomeId, scaffoldIds, containedMarkerGenes):

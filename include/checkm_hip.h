@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_* and ckm_nhmm_* */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_*, ckm_nhmm_* and ckm_select_* */
 
 enum {
   CKM_OK      =  0,
@@ -830,6 +830,47 @@ typedef struct {
 typedef ckm_sim_info ckm_simscaf_info;
 int  ckm_simscaf_check(const ckm_simscaf_args *a);
 int  ckm_simscaf_run(ckm_ctx *ctx, const ckm_simscaf_args *a, uint64_t budget_bytes, double *out, ckm_simscaf_info *info);
+
+/* ---- MarkerSetSelection: sampled genomes drawn and scored on the device (additions to ABI 12) ---------------------------------
+ * Replaces the replicate loop of scripts/simInferBestMarkerSet.py (:94-110): per replicate two random.uniform, MarkerSetBuilder.sampleGenome
+ * (scripts/genometreeworkflow/markerSetBuilder.py:265-289), containedMarkerGenes and both modes of MarkerSet.genomeCheck for every marker
+ * set.  The draws come from a counter-based generator on the device.  checkm_amd/csrc/select_dev.h, kernels_select.hip.
+ *
+ * Genomes: ngenomes test genomes of genome_len[g] bases, C_g = genome_len[g] / contig_len contigs each.  Keys: for cell (g, m) =
+ * g * nmarkers + m, key[key_off[cell] .. key_off[cell + 1] - 1] are the start positions p[0] of the copies of marker m in genome g (nkeys
+ * entries in all).  The marker sets are ckm_sim_args' ms_off / cs_off / cs_marker.  Every offset table starts at 0 and never falls.
+ *
+ * Draw (g, r), r < nreplicates, from Philox4x32-10 with the key (seed & 0xffffffff, seed >> 32) and the counter (index, r, g, stream):
+ * stream 0 gives the two fractions (u = 53 bits of two words * 2^-53; lo + (hi - lo) * u), nComp = (int)(C * testComp + 0.5), nCont
+ * likewise, trueComp = (double)nComp * contig_len * 100 / genome_len; stream 1 gives contig i the word w_i, and the nComp contigs with the
+ * smallest pairs (w_i, i) are taken once each; stream 2 gives contamination draw j the contig ((uint64)w_j * C) >> 32.  A copy at p counts
+ * the multiplicity of contig p / contig_len where that is below C, else 0; a marker's count is the sum over its copies.
+ *
+ * out->truth holds trueComp and trueCont per draw, truth[(g * nreplicates + r) * 2 ..]; out->out four float64 per (draw, marker set),
+ * out[((g * nreplicates + r) * nsets + s) * 4 ..], as ckm_sim_run's; out->rows, where not NULL, min(multiplicity, 65535) of every contig,
+ * genome g's rows [nreplicates][C_g] behind those of the genomes before it.  One launch covers the draws of a round; a call goes in rounds
+ * of whole draws within budget_bytes (0: CKM_SELECT_BATCH_MB, default 256, << 20; a round holds at least one draw), which never changes
+ * a result.  info may be NULL.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, an offset table that does not start at 0, falls or points beyond its table, a
+ * marker index beyond the markers, a co-located set without a member, a marker set without a co-located set; CKM_ERANGE for a key outside
+ * [0, 2^31), a contig_len outside [1, 2^31), a genome with no contig (C = 0) or with more than 16384, a completeness range outside [0, 1]
+ * or a contamination range outside [0, 8] (not finite, or lo > hi), more than 65535 contamination draws, copies of a marker times
+ * (contamination draws + 1) beyond 2^32 - 1, more than 2^24 genomes, markers or replicates, more than 2^31 - 1 draws or cells, more than
+ * 2^20 marker sets.  ckm_select_check applies the same tests and needs no device: the caller then computes such a call with its own loop. */
+typedef struct {
+  uint32_t        ngenomes;    const int64_t  *genome_len;
+  uint32_t        nmarkers;    const uint64_t *key_off;  const int64_t *key;        uint64_t nkeys;
+  uint32_t        nsets;       const uint64_t *ms_off;   const uint64_t *cs_off;    uint64_t ncs;
+  const uint32_t *cs_marker;   uint64_t        nmembers;
+  uint32_t        nreplicates; int64_t         contig_len;
+  double          comp_lo, comp_hi, cont_lo, cont_hi;
+  uint64_t        seed;
+} ckm_select_args;
+typedef struct { double *truth; double *out; uint16_t *rows; } ckm_select_out;
+typedef ckm_sim_info ckm_select_info;
+int  ckm_select_check(const ckm_select_args *a);
+int  ckm_select_run(ckm_ctx *ctx, const ckm_select_args *a, uint64_t budget_bytes, const ckm_select_out *out, ckm_select_info *info);
 
 /* ---- PplacerRunner: bins placed on the edges of the reference tree (additions to ABI 12) -------------------------------------
  * Replaces the pplacer call of checkm/pplacer.py:70-80 by a grid search on the device.  checkm_amd/csrc/place_dev.h, kernels_place.hip.
