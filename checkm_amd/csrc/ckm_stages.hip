@@ -81,8 +81,9 @@ int ssv_class(const HostProfile &hp) { return hp.ssv8Q ? 100 + hp.ssv8Q : hp.ssv
 uint32_t ssv_per_block(int cls) { return (uint32_t)ssv_threads_for(cls) / 64u * (cls >= 100 ? 8u : 4u) * 4u; }      // sequences a workgroup takes: four rounds of its wavefronts
 
 int ssv_threads_for(int Q) {
+  const size_t lds8 = Q >= 100 ? (size_t)ssv8_lds_bytes(Q - 100) : 0;   // (the even and the odd emission image where the class takes the two-alignment row)
   if (Q >= 100) Q -= 100;
-  const size_t lds = (size_t)NROWS * ((Q + 3) / 4) * 256;
+  const size_t lds = lds8 ? lds8 : (size_t)NROWS * ((Q + 3) / 4) * 256;
   // (other limits -- 16 / 32 KB, 8 / 16 KB -- were measured in round 3, profiles/r03m_ssv_threads.txt: no difference beyond noise)
   if (lds <= 40 * 1024) return 256;
   if (lds <= 80 * 1024 || Q > 40) return 512;   // kernels with Q > 40 are compiled for <= 512 threads (256 VGPRs)

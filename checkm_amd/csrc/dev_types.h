@@ -24,7 +24,8 @@ struct DevModel {
   // tables in HBM
   const int16_t *ssv_tbl;   // [Qg][30][16][8]  bias - cost as int16 (msv16_kernel, the exact MSV stage)
   const uint16_t *ssv_tbl_h; // same layout, (bias - cost)/256 as IEEE half bits (ssv_kernel_h)
-  const uint16_t *ssv8_tbl_h; // [Qg8][30][2 copies][8 lanes][8] the 8-lane image of models of <= 512 nodes (ssv_kernel_h8), or null
+  const uint16_t *ssv8_tbl_h; // [Qg8][30][2 copies][8 lanes][8] the 8-lane image of models of <= 512 nodes (ssv_kernel_h8), or null;
+                              // [2 alignments][Qg8][30][2 copies][8 lanes][8] where ssv8_two_alignments(M, Q8) holds
   const uint8_t *rbv;       // [29][M+1]
   const uint32_t *vit_e;    // [30][vitQH][64] packed emission words (cell j | cell j+QH of each lane)
   const uint32_t *vit_t;    // [8][vitQH][64]  packed transition words: BM MM IM DM (into) MD MI II DD (from)
@@ -33,6 +34,17 @@ struct DevModel {
   const float   *rf;        // [30][Mp]
   const float   *ftr;       // [8][Mp]
 };
+
+// The 8-lane SSV kernel's two-alignment row (kernels_ssv.hip): the classes that take it, and of those the models that leave the last
+// cell of the class out of the model (the cell no lane holds at odd rows).  A model that fills its class keeps the striped image and
+// row.  In LDS the odd image lies right behind the even one, and its base travels in the ds_read offset field with the group index:
+// (2 Qg - 1) * 7680 <= 65535 holds up to Qg = 4, 16 registers per lane (why the larger classes stay out: DESIGN.md section 3).
+constexpr int SSV_GROUP_BYTES = 30 * 256;          // one register group of an emission image: 30 symbols x 256 B
+constexpr int SSV8_TWO_MAX_Q = 16;
+constexpr bool ssv8_two_alignments_class(int Q8) { return Q8 >= 1 && Q8 <= SSV8_TWO_MAX_Q; }
+constexpr bool ssv8_two_alignments(int M, int Q8) { return ssv8_two_alignments_class(Q8) && M < 16 * Q8; }
+constexpr int ssv8_odd_base(int Q8) { return (Q8 + 3) / 4 * SSV_GROUP_BYTES; }
+constexpr int ssv8_lds_bytes(int Q8) { return (ssv8_two_alignments_class(Q8) ? ssv8_odd_base(Q8) : 0) + (Q8 + 3) / 4 * SSV_GROUP_BYTES; }
 
 // length-dependent specials, indexed by sequence length L
 struct LenEntry {

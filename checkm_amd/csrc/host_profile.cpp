@@ -11,6 +11,7 @@
 #include <thread>
 #include <memory>
 #include "ckm_internal.h"
+#include "dev_types.h"
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
@@ -398,7 +399,23 @@ HostProfile configure_profile(const HostHMM &h) {
     static const int kSsv8Q[] = {2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 18, 20, 22, 24, 26, 28, 30, 32};
     p.ssv8Q = 0;
     for (int q : kSsv8Q) if (q * 16 >= M) { p.ssv8Q = q; break; }
-    if (p.ssv8Q) {
+    if (p.ssv8Q && ssv8_two_alignments(M, p.ssv8Q)) {
+      // Two alignments of CONSECUTIVE cells: lane z owns cells z * 2 Q8 .. (z + 1) * 2 Q8 - 1 and a register holds two adjacent ones.  Even
+      // image: register j = cells (2j, 2j + 1) of the lane; odd image: (2j - 1, 2j), the even one shifted by one cell, so that the kernel's
+      // odd rows are a rename plus a WHOLE-register carry from the previous lane and its even rows are in place.  Cell -1 of lane 0 and every
+      // cell beyond the model are impossible; the last cell of the class is one of them (M < 16 Q8), which is what lets the odd rows go
+      // without it.  Each image keeps the [group][symbol][2 copies][8 lanes][16 B] rows of the striped one.
+      const int Q8 = p.ssv8Q, Qg8 = (Q8 + 3) / 4;
+      const size_t image = (size_t)NROWS * Qg8 * 128;
+      p.ssv8_tbl_h.assign(2 * image, half_bits_of_256th(p.bias_b - 255));
+      for (int odd = 0; odd < 2; ++odd)
+        for (int x = 0; x < KP; ++x) for (int q = 0; q < Q8; ++q) for (int z = 0; z < 8; ++z) for (int hh = 0; hh < 2; ++hh) {
+          const int k = z * 2 * Q8 + 2 * q + hh - odd + 1;
+          const int cost = (k >= 1 && k <= M) ? p.rbv[(size_t)x * (M + 1) + k] : 255;
+          for (int c = 0; c < 2; ++c)
+            p.ssv8_tbl_h[(size_t)odd * image + (((((size_t)(q / 4) * NROWS + x) * 2 + c) * 8 + z) * 8) + (size_t)(q % 4) * 2 + hh] = half_bits_of_256th(p.bias_b - cost);
+        }
+    } else if (p.ssv8Q) {
       const int Q8 = p.ssv8Q, Qg8 = (Q8 + 3) / 4;
       p.ssv8_tbl_h.assign((size_t)NROWS * Qg8 * 128, half_bits_of_256th(p.bias_b - 255));
       for (int x = 0; x < KP; ++x) for (int q = 0; q < Q8; ++q) for (int z = 0; z < 8; ++z) for (int hh = 0; hh < 2; ++hh) {

@@ -21,7 +21,8 @@
 // p = q + Q*(2*lane16 + half) so the diagonal move i-1,k-1 -> i,k is a register rename plus ONE row_shr DPP
 // move per row.  Emission words of the model live in LDS as [Q/4][symbol][16 lanes][16 B]: each row step is
 // ceil(Q/4) conflict-free ds_read_b128 per lane (address = one v_perm_b32 of the residue word over the lane
-// offset, the group index in the offset field).
+// offset, the group index in the offset field).  The 8-lane classes of up to 16 registers hold consecutive cells in two
+// alignments instead (ssv_rows2_h2 below): a whole-register carry every second row and no v_alignbit_b32.
 //
 // Round 4: the lane that holds a pair's Smax finishes the MSV stage itself (ssv_finish below) -- byte score,
 // overflow / J-state / Smax == 0 routing, F1 -- and appends the pair to the survivor or the exact-MSV table;
@@ -44,6 +45,7 @@ constexpr u32 PAD4 = 0x1d1d1d1du;   // four PADCODE (29) residues
 // residue word into byte 1 above the lane offset (symbols < 32, so the image of register group g starts at g * SSV_GSTRIDE
 // and the group index travels in the ds_read offset field).
 constexpr int SSV_GSTRIDE = SSV_NROWS * 256;
+static_assert(SSV_GSTRIDE == SSV_GROUP_BYTES, "dev_types.h sizes the images");
 template <int B>
 __device__ __forceinline__ u32 ssv_addr(u32 word, u32 lane_off) { return __builtin_amdgcn_perm(word, lane_off, 0x0c0c0400u + ((u32)B << 8)); }
 
@@ -106,6 +108,65 @@ __device__ __forceinline__ void ssv_rows2_h(u32 (&U)[Q], u32 &xE, u32 &prev, u32
     xE = pk_max3_h(xE, U[0], v);
     U[0] = v;
   }
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// The two-alignment row: a lane owns 2Q CONSECUTIVE cells and a register holds two adjacent ones, so the lane's window slides one
+// cell per row and the alignment alternates.  Even alignment: register j = cells (2j, 2j + 1) of the lane; odd: (2j - 1, 2j).
+//   row a, even -> odd:  U[j] = clamp(U[j - 1] + Eodd[x][j]); the predecessors of my cells (-1, 0) are the previous lane's cells
+//                        (2Q - 2, 2Q - 1), its WHOLE top register: one DPP move, no v_alignbit_b32
+//   row b, odd -> even:  U[j] = clamp(U[j] + Eeven[x][j]), in place, nothing crosses a lane
+// 3Q + 2 v_perm_b32 + 1 DPP move per two rows, against 3Q + 2 + 2 + 2 of the striped row above: 1.5 Q + 1.5 per row.  The same integer
+// recurrence on the same cells.  The lanes without a predecessor take 0 (bound_ctrl), and their cell -1 has the impossible emission.
+// At odd rows no lane holds the last cell of the class, so this row serves the models that leave that cell out (ssv8_two_alignments,
+// dev_types.h; the host builds the two images for exactly those).  The odd image lies behind the even one and its base travels in the
+// ds_read offset field with the group index: (2 Qg - 1) * SSV_GSTRIDE <= 65535 up to Qg = 4, the classes that take this row.
+// --------------------------------------------------------------------------------------------------------------------
+template <int Q, int SHR>
+__device__ __forceinline__ void ssv_rows2_h2(u32 (&U)[Q], u32 &xE, u32 addr_a, u32 addr_b) {
+  constexpr int Qg = (Q + 3) / 4;
+  static_assert(ssv8_odd_base(Q) + (Qg - 1) * SSV_GSTRIDE <= 65535, "the ds_read offset field has 16 bits");
+  u32 e[Qg * 4];
+  ssv_load_row<Q>(e, addr_a + (u32)ssv8_odd_base(Q));
+  {
+    const u32 carry = (u32)__builtin_amdgcn_update_dpp(0, (int)U[Q - 1], SHR, 0xf, 0xf, true);
+#pragma unroll
+    for (int q = Q - 1; q >= 1; --q) U[q] = pk_add_h_clamp(U[q - 1], e[q]);
+    U[0] = pk_add_h_clamp(carry, e[0]);
+  }
+  ssv_load_row<Q>(e, addr_b);
+#pragma unroll
+  for (int q = Q - 1; q >= 0; --q) {
+    const u32 v = pk_add_h_clamp(U[q], e[q]);
+    xE = pk_max3_h(xE, U[q], v);
+    U[q] = v;
+  }
+}
+
+// The row loop of one wavefront round of the 8-lane kernel, in either form; returns the packed running maximum.
+template <int Q, bool TWO>
+__device__ __forceinline__ u32 ssv8_scan(const uint8_t *rp, int L, int Lmax, u32 lane_off) {
+  u32 U[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) U[q] = 0u;
+  u32 xE = 0u, prev = 0u;
+  const int nchunk = (Lmax + 15) >> 4;
+  const uint4 padv = make_uint4(PAD4, PAD4, PAD4, PAD4);
+  uint4 cur = padv;
+  if (0 < L) cur = *reinterpret_cast<const uint4 *>(rp);
+  for (int c = 0; c < nchunk; ++c) {
+    uint4 nxt = padv;
+    if ((c + 1) * 16 < L) nxt = *reinterpret_cast<const uint4 *>(rp + (c + 1) * 16);
+#define CKM_SSV_PAIR(wd, A, B)                                                                                \
+  if constexpr (TWO) ssv_rows2_h2<Q, 0x112>(U, xE, ssv_addr<A>(wd, lane_off), ssv_addr<B>(wd, lane_off));       \
+  else ssv_rows2_h<Q, 0x112>(U, xE, prev, ssv_addr<A>(wd, lane_off), ssv_addr<B>(wd, lane_off));
+#define CKM_SSV_WORD(wd) CKM_SSV_PAIR(wd, 0, 1) CKM_SSV_PAIR(wd, 2, 3)
+    CKM_SSV_WORD(cur.x) CKM_SSV_WORD(cur.y) CKM_SSV_WORD(cur.z) CKM_SSV_WORD(cur.w)
+#undef CKM_SSV_WORD
+#undef CKM_SSV_PAIR
+    cur = nxt;
+  }
+  return xE;
 }
 
 // --------------------------------------------------------------------------------------------------------------------
@@ -226,10 +287,18 @@ __global__ void __launch_bounds__(Q > 40 ? 512 : 1024) ssv_kernel_h8(const SsvBl
   constexpr int ROWB = Qg * 256;
   lds_image_at_zero(smem);
   const SsvBlockWork w = work[blockIdx.x];
+  // block-uniform: the model leaves the last cell of the class out, so its image holds the two alignments (twice the bytes)
+  bool two = false;
+  if constexpr (ssv8_two_alignments_class(Q)) two = ssv8_two_alignments(models[w.model].M, Q);
   {
     const uint4 *src = reinterpret_cast<const uint4 *>(models[w.model].ssv8_tbl_h);
     uint4 *dst = reinterpret_cast<uint4 *>(smem);
-    for (int i = threadIdx.x; i < SSV_NROWS * ROWB / 16; i += blockDim.x) dst[i] = src[i];
+    constexpr int n16 = SSV_NROWS * ROWB / 16;
+    for (int i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+    if (two) {                                                         // the odd image follows the even one in HBM
+      uint4 *dst_odd = reinterpret_cast<uint4 *>(smem + ssv8_odd_base(Q));
+      for (int i = threadIdx.x; i < n16; i += blockDim.x) dst_odd[i] = src[n16 + i];
+    }
   }
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6;
@@ -245,24 +314,9 @@ __global__ void __launch_bounds__(Q > 40 ? 512 : 1024) ssv_kernel_h8(const SsvBl
     Lmax = max(Lmax, max(__builtin_amdgcn_readlane(L, 16), __builtin_amdgcn_readlane(L, 17)));
     Lmax = max(Lmax, max(__builtin_amdgcn_readlane(L, 32), __builtin_amdgcn_readlane(L, 33)));
     Lmax = max(Lmax, max(__builtin_amdgcn_readlane(L, 48), __builtin_amdgcn_readlane(L, 49)));
-    u32 U[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) U[q] = 0u;
-    u32 xE = 0u, prev = 0u;
-    const int nchunk = (Lmax + 15) >> 4;
-    const uint4 padv = make_uint4(PAD4, PAD4, PAD4, PAD4);
-    uint4 cur = padv;
-    if (0 < L) cur = *reinterpret_cast<const uint4 *>(rp);
-    for (int c = 0; c < nchunk; ++c) {
-      uint4 nxt = padv;
-      if ((c + 1) * 16 < L) nxt = *reinterpret_cast<const uint4 *>(rp + (c + 1) * 16);
-#define CKM_SSV_WORD(wd)                                                                            \
-  ssv_rows2_h<Q, 0x112>(U, xE, prev, ssv_addr<0>(wd, lane_off), ssv_addr<1>(wd, lane_off));           \
-  ssv_rows2_h<Q, 0x112>(U, xE, prev, ssv_addr<2>(wd, lane_off), ssv_addr<3>(wd, lane_off));
-      CKM_SSV_WORD(cur.x) CKM_SSV_WORD(cur.y) CKM_SSV_WORD(cur.z) CKM_SSV_WORD(cur.w)
-#undef CKM_SSV_WORD
-      cur = nxt;
-    }
+    u32 xE;
+    if constexpr (ssv8_two_alignments_class(Q)) xE = two ? ssv8_scan<Q, true>(rp, L, Lmax, lane_off) : ssv8_scan<Q, false>(rp, L, Lmax, lane_off);
+    else xE = ssv8_scan<Q, false>(rp, L, Lmax, lane_off);
     u32 mb = max(xE & 0xffffu, xE >> 16);
     mb = max(mb, (u32)__shfl_xor((int)mb, 2, 16));
     mb = max(mb, (u32)__shfl_xor((int)mb, 4, 16));
@@ -317,8 +371,9 @@ int launch_ssv(int Q, int nblocks, int threads, hipStream_t stream, const SsvBlo
     switch (Q - 100) {
 #define X(QV) case QV: {                                                                                         \
       static uint32_t attr8 = 0;                                                                                 \
-      raise_lds_limit(ssv_kernel_h8<QV>, (size_t)SSV_NROWS * ((QV + 3) / 4) * 256, attr8);                       \
-      hipLaunchKernelGGL(ssv_kernel_h8<QV>, dim3(nblocks), dim3(threads), (size_t)SSV_NROWS * ((QV + 3) / 4) * 256, stream, work, models, res, seq_off, seq_len, lists, epi); \
+      constexpr size_t lds8 = (size_t)ssv8_lds_bytes(QV);                                                        \
+      raise_lds_limit(ssv_kernel_h8<QV>, lds8, attr8);                                                           \
+      hipLaunchKernelGGL(ssv_kernel_h8<QV>, dim3(nblocks), dim3(threads), lds8, stream, work, models, res, seq_off, seq_len, lists, epi); \
     } break;
       X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(18) X(20) X(22) X(24) X(26) X(28) X(30) X(32)
 #undef X

@@ -77,6 +77,44 @@ OP3(k_pk_fma_f16, "v_pk_fma_f16 %0, %0, %1, %2")
 MIX(k_mix_i16, "v_pk_add_i16 %2, %0, %3 clamp\n v_pk_max_i16 %1, %1, %2\n v_pk_add_i16 %0, %2, %3 clamp\n v_pk_max_i16 %1, %1, %0")
 MIX(k_mix_f16, "v_pk_add_f16 %2, %0, %3 clamp\n v_pk_add_f16 %0, %2, %3 clamp\n v_pk_maximum3_f16 %1, %1, %2, %0")
 
+// The whole row pair of the 8-lane SSV kernel at Q = 16 registers, fixed part included (the emission operand is the address register:
+// no LDS here).  Striped: per row a v_perm_b32, a DPP move and a v_alignbit_b32 -- 3Q + 6 instructions per two rows.  Two alignments:
+// the odd row renames and takes the previous lane's whole top register (one DPP move), the even row is in place -- 3Q + 3.
+#define PK_ADD(d, s, e) asm volatile("v_pk_add_f16 %0, %1, %2 clamp" : "=v"(d) : "v"(s), "v"(e))
+#define PK_MAX3(m, x, y) asm volatile("v_pk_maximum3_f16 %0, %0, %1, %2" : "+v"(m) : "v"(x), "v"(y))
+#define PERM(d, w, o, sel) asm volatile("v_perm_b32 %0, %1, %2, %3" : "=v"(d) : "v"(w), "v"(o), "s"(sel))
+#define DPP_SHR2(d, s) asm volatile("v_mov_b32_dpp %0, %1 row_shr:2 row_mask:0xf bank_mask:0xf" : "+v"(d) : "v"(s))
+#define ALIGN16(d, hi, lo) asm volatile("v_alignbit_b32 %0, %1, %2, 16" : "=v"(d) : "v"(hi), "v"(lo))
+__global__ void __launch_bounds__(256) k_row2_striped(unsigned *out, unsigned seed) {
+  unsigned a[CH], m = seed, w = seed * 3 + threadIdx.x, off = (threadIdx.x & 15) * 16, prev = 0, ad, carry, t;
+  for (int c = 0; c < CH; ++c) a[c] = seed + threadIdx.x * 7 + c * 0x01010101u;
+  for (int it = 0; it < ITERS / 2; ++it) {
+    PERM(ad, w, off, 0x0c0c0400u); DPP_SHR2(prev, a[CH - 1]); ALIGN16(carry, a[CH - 1], prev);
+    _Pragma("unroll") for (int c = CH - 1; c >= 1; --c) PK_ADD(a[c], a[c - 1], ad);
+    PK_ADD(a[0], carry, ad);
+    PERM(ad, w, off, 0x0c0c0500u); DPP_SHR2(prev, a[CH - 1]); ALIGN16(carry, a[CH - 1], prev);
+    _Pragma("unroll") for (int c = CH - 1; c >= 1; --c) { PK_ADD(t, a[c - 1], ad); PK_MAX3(m, a[c], t); a[c] = t; }
+    PK_ADD(t, carry, ad); PK_MAX3(m, a[0], t); a[0] = t;
+  }
+  unsigned r = m;
+  for (int c = 0; c < CH; ++c) r ^= a[c];
+  out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+}
+__global__ void __launch_bounds__(256) k_row2_two_alignments(unsigned *out, unsigned seed) {
+  unsigned a[CH], m = seed, w = seed * 3 + threadIdx.x, off = (threadIdx.x & 15) * 16, carry = 0, ad, t;
+  for (int c = 0; c < CH; ++c) a[c] = seed + threadIdx.x * 7 + c * 0x01010101u;
+  for (int it = 0; it < ITERS / 2; ++it) {
+    PERM(ad, w, off, 0x0c0c0400u); DPP_SHR2(carry, a[CH - 1]);
+    _Pragma("unroll") for (int c = CH - 1; c >= 1; --c) PK_ADD(a[c], a[c - 1], ad);
+    PK_ADD(a[0], carry, ad);
+    PERM(ad, w, off, 0x0c0c0500u);
+    _Pragma("unroll") for (int c = CH - 1; c >= 0; --c) { PK_ADD(t, a[c], ad); PK_MAX3(m, a[c], t); a[c] = t; }
+  }
+  unsigned r = m;
+  for (int c = 0; c < CH; ++c) r ^= a[c];
+  out[blockIdx.x * blockDim.x + threadIdx.x] = r;
+}
+
 template <class F>
 double timeit(F launch) {
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
@@ -115,5 +153,6 @@ int main() {
            1.0 / (rows / (ms * 1e-3) / (p.multiProcessorCount * 4) / clk), ninst);                               \
   }
   RUNMIX(k_mix_i16, "row body packed i16", 4) RUNMIX(k_mix_f16, "row body packed f16+max3", 3)
+  RUNMIX(k_row2_striped, "row pair striped Q=16", 3 * CH + 6) RUNMIX(k_row2_two_alignments, "row pair two alignments Q=16", 3 * CH + 3)
   return 0;
 }
