@@ -2,16 +2,28 @@
 import ctypes as C
 import os
 import subprocess
+import threading
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "_build", "libp7oracle.so")
+_FB_LIB = os.path.join(_HERE, "_build", "libfbplain.so")
+
+
+_build_lock = threading.Lock()     # (the references' worlds first call in from a thread pool)
 
 
 def build(force=False):
+    with _build_lock:
+        return _build(force)
+
+
+def _build(force):
     src = [os.path.join(_HERE, f) for f in ("p7oracle.c", "p7oracle.h", "p7simd.c", "p7simd.h", "Makefile")]
-    if force or not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in src):
+    fb = [os.path.join(_HERE, f) for f in ("fb_plain.c", "Makefile")]
+    if force or not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in src) or \
+            not os.path.exists(_FB_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_FB_LIB) for s in fb):
         subprocess.check_call(["make", "-s", "-C", _HERE])
     return _LIB
 
@@ -81,6 +93,26 @@ def lib():
                                           C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32)]
         _lib = L
     return _lib
+
+
+_fb = None
+
+
+def fb_plain():
+    """oracle/fb_plain.c: the scalar loop of tests/fb_reference.py, as fbp_<name>_f64, _f32 and _f80 (long double).  It takes the parameter arrays
+    the caller parsed from the HMM text and shares nothing with the oracle above."""
+    global _fb
+    if _fb is None:
+        build()
+        L = C.CDLL(_FB_LIB)
+        P, I = C.c_void_p, C.c_int
+        for sfx in ("_f64", "_f32", "_f80"):
+            getattr(L, "fbp_forward" + sfx).argtypes = [I, P, P, P, P, P, I, P, P]
+            getattr(L, "fbp_occupancy" + sfx).argtypes = [I, P, P, P, P, P, I, P, P, P, P]
+            getattr(L, "fbp_envelope" + sfx).argtypes = [I, P, P, P, P, P, I, P, P, P, P, P, P, P, P]
+            getattr(L, "fbp_bias" + sfx).argtypes = [P, P, P, I, P]
+        _fb = L
+    return _fb
 
 
 def set_simd(on):
