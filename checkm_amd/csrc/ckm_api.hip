@@ -37,7 +37,8 @@ extern "C" int ckm_device_count(int *n) {
 
 extern "C" int ckm_ctx_create(int device, ckm_ctx **out) {
   // The per-register-class launches of the rare stages overlap on up to 8 streams; the runtime's default of 4 hardware
-  // queues would serialise half of them.  Only effective if HIP has not been initialised in this process yet.
+  // queues would serialise half of them.  Only effective if HIP has not been initialised in this process yet, and only where the
+  // variable is not set: an inherited value stays, and the device's stream pool keeps within it (stream_plan.h).
   setenv("GPU_MAX_HW_QUEUES", "16", 0);
   return guarded([&] {
     if (!out) throw Error(CKM_EINVAL, "out is NULL");
@@ -64,20 +65,29 @@ extern "C" int ckm_ctx_create(int device, ckm_ctx **out) {
     // (a quarter of what is free: MarkerGeneFinder.find keeps up to three contexts per device in flight, each with its own workspace)
     if (hipMemGetInfo(&fre, &tot) == hipSuccess) budget = std::min<size_t>((size_t)96 << 30, fre / 4) / ctx->nworkers;
     if (const char *e = getenv("CKM_WS_BUDGET_MB")) budget = std::max<size_t>(16, strtoull(e, nullptr, 10)) << 20;   // tests: force several envelope batches
+    // A context of one lane (the default) takes its normal-priority streams from the device's pool, which holds no more streams than
+    // the process has hardware queues (stream_plan.h); the contexts of a device take the plan's context slots in turn.
+    const bool pooled = ctx->nworkers == 1;
     const int nside = choose_side_streams(ctx->nworkers);
+    const int slot = pooled ? pool_next_slot(device) : 0;
     for (auto &w : ctx->w) {
       w.device = device; w.id = (int)(&w - ctx->w);
       if (&w - ctx->w >= ctx->nworkers) continue;
-      // non-blocking streams: nothing here may synchronise implicitly with the null stream or with another worker's streams
-      HIPCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-      w.nside = nside;
-      for (int k = 0; k < 16; ++k) {
-        if (k >= nside) { w.side[k] = w.side[k % nside]; continue; }
-        HIPCHK(hipStreamCreateWithFlags(&w.side[k], hipStreamNonBlocking));
+      if (pooled) pool_assign_streams(w, device, slot);
+      else {
+        // non-blocking streams: nothing here may synchronise implicitly with the null stream or with another worker's streams
+        w.own_streams = true;
+        HIPCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+        w.nside = nside;
+        w.nss = nside >= 8 ? 4 : std::max(1, nside / 3); w.nch = nside - w.nss;
+        for (int k = 0; k < 16; ++k) {
+          if (k >= nside) { w.side[k] = w.side[k % nside]; continue; }
+          HIPCHK(hipStreamCreateWithFlags(&w.side[k], hipStreamNonBlocking));
+        }
+        // the trace ensembles of a search get a stream of their own: a launch lasts as long as its longest region (tens of milliseconds), and
+        // neither a chain stream nor the priority stream (which carries the NEXT batch's uploads) may queue behind it
+        HIPCHK(hipStreamCreateWithFlags(&w.ens_stream, hipStreamNonBlocking));
       }
-      // the trace ensembles of a search get a stream of their own: a launch lasts as long as its longest region (tens of milliseconds), and
-      // neither a chain stream nor the priority stream (which carries the NEXT batch's uploads) may queue behind it
-      HIPCHK(hipStreamCreateWithFlags(&w.ens_stream, hipStreamNonBlocking));
       {
         // the rounds after a search's drain (envelopes of the ensembles' clustering, deferred regions: milliseconds of device work the
         // host waits for) must not queue behind ANOTHER context's SSV launches, whose backlog holds the normal-priority hardware queues
@@ -139,8 +149,9 @@ extern "C" void ckm_ctx_destroy(ckm_ctx *ctx) {
     for (auto &e : w.cls_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : w.grp_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : w.ens_ev) if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < w.nside; ++k) (void)hipStreamDestroy(w.side[k]);
     if (w.late[0]) (void)hipStreamDestroy(w.late[0]);
+    if (!w.own_streams) continue;                      // (handles of the device's pool: they live as long as the process)
+    for (int k = 0; k < w.nside; ++k) (void)hipStreamDestroy(w.side[k]);
     if (w.ens_stream) (void)hipStreamDestroy(w.ens_stream);
     (void)hipStreamDestroy(w.stream);
   }

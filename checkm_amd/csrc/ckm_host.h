@@ -23,6 +23,7 @@
 #include "ckm_internal.h"
 #include "dev_types.h"
 #include "host_pool.h"
+#include "stream_plan.h"
 
 namespace ckm {
 
@@ -265,8 +266,10 @@ struct Worker {
   int id = 0;
   hipStream_t stream = nullptr;
   hipStream_t ens_stream = nullptr;       // trace ensembles run beside the envelope stage
-  hipStream_t side[16];                    // per-register-class launches of the rare stages overlap on these (the first side_streams() are distinct, the rest alias them)
-  int nside = 0;                          // distinct side streams owned
+  hipStream_t side[16];                    // per-register-class launches of the rare stages overlap on these (the first nside are distinct, the rest alias them)
+  int nside = 0;                          // distinct side streams: side[0 .. nss) carry SSV launches, side[nss .. nss + nch) the groups' chains (stream_plan.h)
+  int nss = 0, nch = 0;
+  bool own_streams = false;               // false: stream, side[] and ens_stream are handles into the device's stream pool (never destroyed); true: a lane of a multi-lane context, with streams of its own
   hipEvent_t ev[8];
   ckm_search_stats stats;
   // reusable device scratch
@@ -454,8 +457,11 @@ float finish_forward(float xC, float move, const std::vector<float> &scales);
 int ssv_threads_for(int Q);
 int ssv_class(const HostProfile &hp);
 uint32_t ssv_per_block(int cls);
-int side_streams();
-int choose_side_streams(int nworkers);
+int choose_side_streams(int nworkers);                   // side streams of one lane of a multi-lane context (CKM_WORKERS > 1), which owns its streams
+int hw_queue_budget();                                   // hardware queues the process runs with (stream_plan.h: parse_queue_budget), read once
+void pool_assign_streams(Worker &w, int device, int slot);   // ckm_search.hip: the worker's stream, side[] and ens_stream from the device's pool, by the plan
+int pool_next_slot(int device);                          // context slots of a device, handed out in turn
+hipStream_t fb_side_stream(const Worker *w, size_t gi); // the gi-th register class of a host-driven rare stage
 void trace_pt(const Worker *w, const char *label);      // CKM_TRACE=1: worker / ms since the search began / label on stderr
 void trace_begin();
 void run_fb(Worker *ctx, const ckm_profiles *p, const ckm_seqs *s, FbBatch &b, bool do_fwd, bool do_bwd, bool do_oa,

@@ -180,7 +180,7 @@ static void cascade(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profiles
           // sequences -- is covered by the next launch; ev[0]..ev[1] on the main stream brackets all of them.  The SSV lanes finish
           // the MSV stage themselves (survivor / exact-MSV tables); a table that overflowed means the launches run again with larger ones.
           const SsvEpi epi{lt, ctx->surv.as<PairRec>(), ctx->counters.as<uint32_t>(), cap_surv, ctx->nores.as<PairRec>(), ctx->counters.as<uint32_t>() + 1, cap_nores, nullptr};
-          const int NS = std::min(4, side_streams());
+          const int NS = ctx->own_streams ? std::min(4, ctx->nside) : ctx->nss;      // (pooled: the SSV handles of the plan, 4 with 16 queues or more)
           for (int k = 0; k < NS; ++k) HIPCHK(hipStreamWaitEvent(ctx->side[k], ctx->ev[0], 0));
           int gi = 0;
           for (auto it = groups.rbegin(); it != groups.rend(); ++it, ++gi) {
@@ -284,13 +284,13 @@ static void cascade(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profiles
           auto &g = grp[k];
           uint32_t *qd = ctx->vitq.as<uint32_t>() + k;
           const uint32_t cnt = (uint32_t)g.second.second;
-          if (launch_vit(g.first, std::min<uint32_t>((cnt + 3) / 4, 2048), ctx->side[gi % std::min(4, side_streams())],
+          if (launch_vit(g.first, std::min<uint32_t>((cnt + 3) / 4, 2048), fb_side_stream(ctx, (size_t)gi % 4),
                          WorkQueue{ctx->fbidx.as<uint32_t>() + g.second.first, qd, cnt}, ctx->cand.as<PairRec>(), dm, lt, res, off, dlen,
                          ctx->vitx.as<int32_t>(), ctx->vits.as<float>(), ctx->vitf.as<uint32_t>(), fast, nullptr))
             throw Error(CKM_ERANGE, "no Viterbi kernel instance for this model length");
         }
         HIPCHK(hipGetLastError());
-        for (int k = 0; k < 4; ++k) HIPCHK(hipStreamSynchronize(ctx->side[k]));
+        for (size_t k = 0; k < 4; ++k) HIPCHK(hipStreamSynchronize(fb_side_stream(ctx, k)));
       };
       run_vit(groups, true);
       ctx->h_a.ensure(cands.size() * 4 + 16); ctx->h_b.ensure(cands.size() * 4 + 16);
@@ -463,6 +463,44 @@ template <class T> T *pin_table(PinnedBuf &b, size_t n) { b.ensure(std::max<size
 // One SSV phase at a time per device, across contexts (see cascade_dev).  The events belong to the baton and live as long as the process.
 struct DeviceBaton { std::mutex m; hipEvent_t ev[2] = {nullptr, nullptr}; int k = 0; bool recorded = false; std::atomic<int> searches{0}; };
 static DeviceBaton &device_baton(int dev) { static DeviceBaton b[64]; return b[(unsigned)dev & 63]; }
+// The normal-priority streams of a device, process-wide: created once, in handle order (stream_plan.h), never more of them than the
+// process has hardware queues, and never destroyed.  A context's stream, side[] and ens_stream are handles into it.  Contexts that share
+// a handle queue their work on it in the order their searches take the baton; no kernel of the cascade waits on memory that a later
+// launch writes (the stages are ordered by stream order and events alone), so sharing a handle delays work and cannot hang it.
+// CKM_CTX_IN_FLIGHT: contexts that get 16 handles of their own where the budget holds them (default 2, as find() keeps).
+struct StreamPool { std::mutex m; std::vector<hipStream_t> h; StreamPlan plan; int next_slot = 0; };
+static StreamPool &stream_pool(int dev) { static StreamPool p[64]; return p[(unsigned)dev & 63]; }
+int ckm::pool_next_slot(int device) {
+  StreamPool &sp = stream_pool(device);
+  std::lock_guard<std::mutex> lock(sp.m);
+  return sp.next_slot++ % kPlanContexts;
+}
+void ckm::pool_assign_streams(Worker &w, int device, int slot) {
+  StreamPool &sp = stream_pool(device);
+  std::lock_guard<std::mutex> lock(sp.m);
+  if (sp.h.empty()) {
+    const int nctx = getenv("CKM_CTX_IN_FLIGHT") ? atoi(getenv("CKM_CTX_IN_FLIGHT")) : 2;
+    sp.plan = stream_plan(hw_queue_budget(), nctx);
+    if (const char *e = getenv("CKM_STREAM_LAYOUT")) {           // measurements, below 16 queues: "SSV,chain,ensembles(0|1),mains" handles
+      int a = 0, b = 0, c = 0, d = 0;
+      if (sp.plan.budget < 16 && sscanf(e, "%d,%d,%d,%d", &a, &b, &c, &d) == 4 && a >= 1 && a <= 4 && b >= 0 && b <= 10 && (c == 0 || c == 1) && d >= 0 &&
+          d <= kPlanContexts && a + b + c + d <= sp.plan.budget)
+        plan_layout(sp.plan, a, b, c, d);
+    }
+    std::vector<hipStream_t> h((size_t)sp.plan.nhandles, nullptr);
+    // non-blocking streams: nothing here may synchronise implicitly with the null stream
+    for (auto &s : h) HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    sp.h = std::move(h);
+  }
+  const StreamPlan &pl = sp.plan;
+  const int c = slot % pl.contexts;
+  w.own_streams = false;
+  w.nss = pl.nss; w.nch = pl.nch; w.nside = pl.nss + pl.nch;
+  w.stream = sp.h[(size_t)pl.main_h[c]];
+  w.ens_stream = sp.h[(size_t)pl.ens_h[c]];
+  for (int k = 0; k < 16; ++k) w.side[k] = sp.h[(size_t)pl.side_h[c][k < w.nside ? k : k % w.nside]];
+}
+
 static bool late_on() { static const bool on = !(getenv("CKM_LATE_PRIO") && atoi(getenv("CKM_LATE_PRIO")) == 0); return on; }
 static bool baton_on() { static const bool on = !(getenv("CKM_SSV_BATON") && atoi(getenv("CKM_SSV_BATON")) == 0); return on; }
 
@@ -717,9 +755,9 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   ensure_ens_seeds(ctx);
   float *ws = ctx->ws.as<float>();
   CKM_TRACE_PT("tables ready");
-  const int NS = side_streams();
-  const int NSS = NS >= 8 ? 4 : std::max(1, NS / 3); // streams of the SSV launches
-  const int NCH = NS - NSS;                        // streams of the groups' chains (none left: a chain follows its SSV launch on the same stream)
+  const int NS = ctx->nside;
+  const int NSS = ctx->nss;                        // streams of the SSV launches (stream_plan.h, by the hardware queues the process runs with)
+  const int NCH = ctx->nch;                        // streams of the groups' chains (none left: a chain follows its SSV launch on the same stream)
 
   // ---- wait for the turn (the lanes' SSV phases run one behind the other on the device: VALU-bound, nothing to gain side by side),
   // queue everything behind the previous lane's SSV launches, pass the turn on ----
@@ -850,21 +888,29 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   for (int k = 0; k < NSS; ++k) { HIPCHK(hipEventRecord(ctx->cls_ev[k], ctx->side[k])); HIPCHK(hipStreamWaitEvent(ms, ctx->cls_ev[k], 0)); }
   HIPCHK(hipEventRecord(ctx->ev[1], ms));                    // ev[0]..ev[1] brackets the lane's SSV launches (with NCH == 0: and the chains queued behind them)
   HIPCHK(hipEventRecord(ctx->cev[1], ms));
+  // the ends of the chain streams, marked before the baton passes: on handles that contexts share, the next search's launches queue
+  // behind these marks
+  for (int k = NSS; k < NS; ++k) HIPCHK(hipEventRecord(ctx->cls_ev[k], ctx->side[k]));
   if (baton_lock.owns_lock()) { baton.k ^= 1; HIPCHK(hipEventRecord(baton.ev[baton.k], ms)); baton.recorded = true; baton_lock.unlock(); }
   {
     std::unique_lock<std::mutex> lock(owner->ssv_mutex);
     owner->ssv_prev_done = ctx->cev[1];
     took_turn = true; owner->ssv_turn++; owner->ssv_cv.notify_all();
   }
-  for (int k = NSS; k < NS; ++k) { HIPCHK(hipEventRecord(ctx->cls_ev[k], ctx->side[k])); HIPCHK(hipStreamWaitEvent(ms, ctx->cls_ev[k], 0)); }
-  if (ctx->ens_pending) { HIPCHK(hipStreamWaitEvent(ms, ctx->ens_ev[16], 0)); ctx->ens_pending = false; }
+  // The chains drain on the ensembles' stream, which ends with this search's last launch anyway: the main stream then carries nothing
+  // that outlasts the SSV phase, and a context that shares the main handle (fewer queues than streams) starts its own SSV phase behind
+  // this one's SSV launches, not behind its chains.  (cev[1]: the bracket ev[0]..ev[1] on the main stream is complete before the host reads it)
+  hipStream_t drain = ctx->ens_stream;
+  for (int k = NSS; k < NS; ++k) HIPCHK(hipStreamWaitEvent(drain, ctx->cls_ev[k], 0));
+  HIPCHK(hipStreamWaitEvent(drain, ctx->cev[1], 0));
+  ctx->ens_pending = false;                                   // (queued on that stream itself)
   // ---- counters last ----
-  HIPCHK(hipMemcpyAsync(h_cnt, d_gcnt, (NG + 1) * CC_SIZE * sizeof(uint32_t), hipMemcpyDeviceToHost, ms));
+  HIPCHK(hipMemcpyAsync(h_cnt, d_gcnt, (NG + 1) * CC_SIZE * sizeof(uint32_t), hipMemcpyDeviceToHost, drain));
   unsigned long long *h_tops = pin_table<unsigned long long>(ctx->h_tops, 4);
-  HIPCHK(hipMemcpyAsync(h_tops, d_tops, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ms));
+  HIPCHK(hipMemcpyAsync(h_tops, d_tops, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, drain));
   HIPCHK(hipGetLastError());
   CKM_TRACE_PT("chain queued");
-  HIPCHK(hipStreamSynchronize(ms));                           // ---- the one synchronisation of the lane ----
+  HIPCHK(hipStreamSynchronize(drain));                          // ---- the one synchronisation of the lane ----
   CKM_TRACE_PT("chain drained");
   if (stop < 99) {
     fprintf(stderr, "ckm-chain w%d stop=%d:", ctx->id, stop);

@@ -63,16 +63,24 @@ float finish_forward(float xC, float move, const std::vector<float> &scales) {
 }
 
 // Side streams a worker spreads the register classes of one stage over.  All workers together must stay within the
-// hardware queues of the device (GPU_MAX_HW_QUEUES = 16): streams that share a queue run their kernels one behind the
+// hardware queues the process runs with: streams that share a queue run their kernels one behind the
 // other, and a short launch of one worker then waits behind a long one of another (measured: the Forward parser of the
-// short class, 1 ms of work, finished 12 ms late behind the envelope kernels of the long class).  So a worker creates
-// main stream + NS side streams with nworkers * (1 + NS) <= 15 and aliases the rest.
-static int g_side_streams = 8;
-int side_streams() { return g_side_streams; }
-int choose_side_streams(int nworkers) {
-  int n = std::max(1, std::min(14, 15 / std::max(1, nworkers) - 1));
-  g_side_streams = n;
-  return n;
+// short class, 1 ms of work, finished 12 ms late behind the envelope kernels of the long class).  A context of one lane (the
+// default) takes its streams from the device's pool by the plan of stream_plan.h; the lanes of a multi-lane context
+// (CKM_WORKERS > 1) each create a main stream + NS side streams with nworkers * (1 + NS) <= 15 and alias the rest.
+int choose_side_streams(int nworkers) { return std::max(1, std::min(14, 15 / std::max(1, nworkers) - 1)); }
+
+// Read at the first context creation, after ckm_ctx_create has set GPU_MAX_HW_QUEUES where nothing was inherited.
+int hw_queue_budget() {
+  static const int b = parse_queue_budget(getenv("CKM_HW_QUEUES"), getenv("GPU_MAX_HW_QUEUES"));
+  return b;
+}
+
+// The host-driven rare stages (persistent queue kernels per register class) keep off the SSV handles where the plan separates them
+// -- another context's SSV launches may be queued there for seconds; with 16 queues or more they go round all side streams as ever.
+hipStream_t fb_side_stream(const Worker *w, size_t gi) {
+  if (w->own_streams || hw_queue_budget() >= 16 || w->nch == 0) return w->side[gi % (size_t)w->nside];
+  return w->side[w->nss + gi % (size_t)w->nch];
 }
 
 // The SSV LAUNCH CLASS of a model: its 16-lane register class (1..64), 100 + its 8-lane class for models of up to 512 nodes,
@@ -147,7 +155,7 @@ void run_fb(Worker *ctx, const ckm_profiles *p, const ckm_seqs *s, FbBatch &b, b
   size_t gi = 0;
   for (size_t g = 0; g < groups.size(); ++g) {
     const Group &gr = groups[g];
-    hipStream_t st = late ? ctx->late[gi++ % 4] : ctx->side[gi++ % side_streams()];
+    hipStream_t st = late ? ctx->late[gi % 4] : fb_side_stream(ctx, gi); ++gi;
     uint32_t *qcd = ctx->fbmodel.as<uint32_t>() + g;
     const uint32_t *lst = ctx->fbidx.as<uint32_t>() + gr.first;
     const uint32_t nb = fb_grid(gr.count);
@@ -285,7 +293,7 @@ void run_msv_exact(Worker *ctx, const ckm_profiles *p, const ckm_seqs *s, const 
   int gi = 0;
   for (auto &g : groups) {
     const size_t first = g.second.first; const uint32_t cnt = (uint32_t)g.second.second;
-    hipStream_t st = ctx->side[gi % side_streams()];
+    hipStream_t st = fb_side_stream(ctx, gi);
     const WorkQueue q{nullptr, ctx->msvlist.as<uint32_t>() + gi, cnt};
     ++gi;
     if (g.first == 1000)
