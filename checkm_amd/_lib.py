@@ -260,6 +260,22 @@ class NhmmInfo(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("tiles", "launches", "cells", "batches")] + [(f, C.c_double) for f in _NHMM_MS]
 
 
+class GtreeArgs(C.Structure):
+    _fields_ = [("nrows", C.c_uint32), ("ncols", C.c_uint32), ("text", C.c_void_p), ("ntext_bytes", C.c_uint64), ("nreps", C.c_uint32), ("cols", C.c_void_p),
+                ("base", C.c_uint32), ("model", C.c_int32), ("max_dist", C.c_double), ("matrix", C.c_void_p), ("nmatrices", C.c_uint32)]
+
+
+class GtreeOut(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("compared", "differ", "dist", "merge_ij", "merge_len")]
+
+
+_GTREE_MS = ("ms_upload", "ms_gather", "ms_counts", "ms_dist", "ms_joins", "ms_download", "ms_total")
+
+
+class GtreeInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("nrounds", "ntrees", "launches")] + [(f, C.c_double) for f in _GTREE_MS]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -299,7 +315,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_aai_check", "ckm_aai_run", "ckm_aai_columns_get", "ckm_aai_free",
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
            "ckm_sim_check", "ckm_sim_run", "ckm_simscaf_check", "ckm_simscaf_run", "ckm_select_check", "ckm_select_run", "ckm_place_check", "ckm_place_run",
-           "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free",
+           "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free", "ckm_gtree_check", "ckm_gtree_host", "ckm_gtree_run",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
 
 _lib = None
@@ -445,6 +461,9 @@ def load():
     L.ckm_nhmm_columns_get.argtypes = [C.c_void_p, C.POINTER(NhmmColumns)]
     L.ckm_nhmm_free.argtypes = [C.c_void_p]
     L.ckm_nhmm_free.restype = None
+    L.ckm_gtree_check.argtypes = [C.POINTER(GtreeArgs)]
+    L.ckm_gtree_host.argtypes = [C.POINTER(GtreeArgs), C.c_uint64, C.POINTER(GtreeOut), C.POINTER(GtreeInfo)]
+    L.ckm_gtree_run.argtypes = [C.c_void_p, C.POINTER(GtreeArgs), C.c_uint64, C.POINTER(GtreeOut), C.POINTER(GtreeInfo)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1852,3 +1871,74 @@ def nhmm_run(ctx, tables, seqs, budget_bytes=0):
         return nhmm_columns(c, info)
     finally:
         load().ckm_nhmm_free(h)
+
+
+GTREE_MODELS = {"kimura": 0, "poisson": 1, "p": 2}
+GTREE_MAX_ROWS, GTREE_MAX_COLS = 1 << 14, 1 << 20
+
+
+class GtreeTables(object):
+    """The arrays of one genome-tree call as ckm_gtree_check / ckm_gtree_run take them (include/checkm_hip.h).  Either an alignment --
+    text: nrows rows of ncols bytes in one uint8 array, cols: the drawn columns of the replicates [nreps, ncols] (or None), base: whether
+    the alignment itself is the first tree, model: 0 / 1 / 2 or its name, max_dist -- or matrices [ntrees, nrows, nrows] float64."""
+
+    def __init__(self, text=None, nrows=0, ncols=0, cols=None, base=True, model="kimura", max_dist=3.0, matrices=None):
+        self.matrices = self.text = self.cols = None
+        self.nreps, self.base, self.max_dist = 0, 1 if base else 0, float(max_dist)
+        self.model = GTREE_MODELS[model] if model in GTREE_MODELS else int(model)
+        if matrices is not None:
+            self.matrices = np.ascontiguousarray(matrices, dtype=np.float64)
+            if self.matrices.ndim != 3 or self.matrices.shape[1] != self.matrices.shape[2]:
+                raise ValueError("matrices are [trees, rows, rows]")
+            self.nrows, self.ncols, self.ntrees = self.matrices.shape[1], 0, self.matrices.shape[0]
+            return
+        self.text = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray)) else text, dtype=np.uint8).reshape(-1)
+        self.nrows, self.ncols = int(nrows), int(ncols)
+        if cols is not None:
+            self.cols = np.ascontiguousarray(cols, dtype=np.uint32).reshape(-1, self.ncols if self.ncols else 1)
+            self.nreps = self.cols.shape[0]
+        self.ntrees = self.base + self.nreps
+
+    def args(self):
+        """The ckm_gtree_args of these arrays (it borrows them: keep this object alive over the call)."""
+        if self.matrices is not None:
+            return GtreeArgs(self.nrows, 0, None, 0, 0, None, 0, 0, self.max_dist, self.matrices.ctypes.data, self.ntrees)
+        return GtreeArgs(self.nrows, self.ncols, _ptr(self.text), self.text.shape[0], self.nreps, _ptr(self.cols) if self.nreps else None, self.base, self.model, self.max_dist,
+                         None, 0)
+
+
+def gtree_check(tables):
+    """ckm_gtree_check: why the alignment, the drawn columns, the model or the matrices of a call would be refused, without a device.
+    Raises CkmError as gtree_run would."""
+    a = tables.args()
+    _chk(load().ckm_gtree_check(C.byref(a)))
+
+
+def _gtree_call(entry, tables, budget_bytes, counts, dist, merges):
+    a = tables.args()
+    _chk(load().ckm_gtree_check(C.byref(a)))                  # (the output shapes below need a call that is in range)
+    N, T = tables.nrows, tables.ntrees
+    with_text = tables.matrices is None
+    o = dict(compared=np.zeros((N, N), dtype=np.uint32) if counts and with_text else None, differ=np.zeros((N, N), dtype=np.uint32) if counts and with_text else None,
+             dist=np.zeros((N, N)) if dist and with_text else None, merge_ij=np.zeros((T, N - 1, 2), dtype=np.uint32) if merges else None,
+             merge_len=np.zeros((T, N - 1, 2)) if merges else None)
+    info = GtreeInfo()
+    go = GtreeOut(*[o[f].ctypes.data if o[f] is not None and o[f].size else None for f in ("compared", "differ", "dist", "merge_ij", "merge_len")])
+    _chk(entry(C.byref(a), int(budget_bytes), C.byref(go), C.byref(info)))
+    o.update({f: int(getattr(info, f)) for f in ("nrounds", "ntrees", "launches")})
+    o.update({f: getattr(info, f) for f in _GTREE_MS})
+    return o
+
+
+def gtree_run(ctx, tables, budget_bytes=0, counts=False, dist=False, merges=True):
+    """The genome-tree pass (ckm_gtree_run).  Returns a dict: compared, differ [nrows, nrows] uint32 (counts) and dist [nrows, nrows]
+    float64 (dist) of the alignment itself, merge_ij [trees, nrows - 1, 2] uint32 and merge_len [trees, nrows - 1, 2] float64 (merges);
+    what was not asked for is None; nrounds, ntrees, launches and the timings in ms."""
+    L = load()
+    return _gtree_call(lambda a, b, o, i: L.ckm_gtree_run(ctx.h, a, b, o, i), tables, budget_bytes, counts, dist, merges)
+
+
+def gtree_host(tables, budget_bytes=0, counts=False, dist=False, merges=True):
+    """The same call through the host executor (ckm_gtree_host): the same bits, no device.  For checks and comparisons; nothing in the
+    package calls it in place of the device."""
+    return _gtree_call(load().ckm_gtree_host, tables, budget_bytes, counts, dist, merges)

@@ -2,7 +2,8 @@
 geneCountTable (:254-287), filterGeneCountTable (:289-309), familyIdToGeneId (:383-395), _genomeSeqLens (:397-406),
 _genomeFamilyPositions (:420-490), the two precompute methods (:408-418, :492-499), geneDistTable (:501-530), the two redundancy
 filters (:555-589), and for the scaffold simulation filterGenomeIds (:42-48), geneIdToScaffoldId (:50-65), _genomeIdToClusterScaffold
-(:311-370) and precomputeGenomeFamilyScaffolds (:372-381).  Plain host code.
+(:311-370) and precomputeGenomeFamilyScaffolds (:372-381), and for the genome tree genomeMetadata / genomeMetadataFromFile (:91-163).
+Plain host code.
 
 A genome <id> is a directory <genomeDir>/<id>/ with <id>.pfam.tab.txt (family in column 8), <id>.tigrfam.tab.txt (family in column
 6), <id>.gff and <id>.fna.  As in the reference: the first line of an annotation table is a header; a column is taken as it stands
@@ -36,6 +37,37 @@ class IMG(object):
 
     def _path(self, genomeId, suffix):
         return os.path.join(self.genomeDir, genomeId, genomeId + suffix)
+
+    # ---- metadata -------------------------------------------------------------------------------------------------------------------
+    def genomeMetadata(self):
+        return self.genomeMetadataFromFile(self.metadataFile)
+
+    def genomeMetadataFromFile(self, metadataFile):
+        """genome -> its row of the metadata table (:91-163), in file order: 'status', 'taxonomy' (the seven ranks from Domain to
+        Species), 'scaffold count', 'GC Count', 'GC %', 'genome size', 'gene count', 'coding base count', 'biotic relationships', 'N50'.
+        Columns are found by their header; every field is stripped; a count that is no integer is 'NA', as in the reference."""
+        def number(text, kind=int):
+            try:
+                return kind(text)
+            except ValueError:
+                return 'NA'
+
+        metadata, col = {}, None
+        ranks = ('Domain', 'Phylum', 'Class', 'Order', 'Family', 'Genus', 'Species')
+        with open(metadataFile) as f:
+            for line in f:
+                fields = [x.strip() for x in line.split('\t')]
+                if col is None:
+                    col = {name: fields.index(name) for name in ('Status', 'Scaffold Count', 'GC Count', 'Genome Size', 'Gene Count', 'Coding Base Count',
+                                                                 'Biotic Relationships', 'N50') + ranks}
+                    continue
+                gc, size = number(fields[col['GC Count']]), number(fields[col['Genome Size']])
+                metadata[fields[0]] = {'status': fields[col['Status']], 'taxonomy': [fields[col[r]] for r in ranks], 'scaffold count': int(fields[col['Scaffold Count']]),
+                                       'GC Count': gc if gc != 'NA' and size not in ('NA', 0) else 'NA',
+                                       'GC %': float(fields[col['GC Count']]) / size if gc != 'NA' and size not in ('NA', 0) else 'NA',
+                                       'genome size': size, 'gene count': number(fields[col['Gene Count']]), 'coding base count': number(fields[col['Coding Base Count']]),
+                                       'biotic relationships': fields[col['Biotic Relationships']], 'N50': int(fields[col['N50']])}
+        return metadata
 
     def filterGenomeIds(self, genomeIds, metadata, fieldToFilterOn, valueToRetain):
         return set(g for g in genomeIds if metadata[g][fieldToFilterOn] == valueToRetain)

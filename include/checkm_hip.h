@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_*, ckm_nhmm_* and ckm_select_* */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_*, ckm_nhmm_*, ckm_select_* and ckm_gtree_* */
 
 enum {
   CKM_OK      =  0,
@@ -947,6 +947,41 @@ int  ckm_nhmm_check(const ckm_nhmm_args *a);
 int  ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucseq *seqs, uint64_t budget_bytes, ckm_nhmm_result **out, ckm_nhmm_info *info);
 int  ckm_nhmm_columns_get(const ckm_nhmm_result *r, ckm_nhmm_columns *out);
 void ckm_nhmm_free(ckm_nhmm_result *r);
+
+/* ---- GenomeTree: pair counts, corrected distances and neighbour joining (additions to ABI 12) --------------------------------
+ * Replaces the FastTree calls of scripts/genometreeworkflow/inferGenomeTree.py and bootstrapTree.py by distances and neighbour joining
+ * of our own definition (checkm_amd/csrc/gtree_dev.h states it), on the device in kernels_gtree.hip.
+ *
+ * Alignment: nrows rows of ncols bytes, row i at text + i * ncols (ntext_bytes = nrows * ncols).  The twenty letters
+ * ARNDCQEGHILKMFPSTWYV in either case are residues, every other byte is "unknown".  Trees of a call: the alignment itself when base is 1,
+ * then one per replicate r, whose column c is column cols[r * ncols + c] of the alignment.  With matrix set the text is not read and
+ * tree t is joined from the nrows x nrows doubles at matrix + t * nrows * nrows (the upper triangle and the lower must agree).
+ * model: 0 Kimura (-ln(1 - p - 0.2 p^2)), 1 Poisson (-ln(1 - p)), 2 p; a pair with nothing compared, a non-positive argument of the
+ * logarithm or a value above max_dist takes max_dist.
+ * Outputs, each may be NULL: compared, differ [nrows][nrows] uint32 and dist [nrows][nrows] of the alignment itself; merge_ij
+ * [trees][nrows - 1][2] (the two slots of a join: a slot names the node last put there, slot i first being row i; the new node takes the
+ * first slot) and merge_len [trees][nrows - 1][2] (the lengths of the edges above the two).  The last row is the root.
+ * budget_bytes (0: CKM_GTREE_BATCH_MB, default 2048, << 20) bounds the trees resident at once (never fewer than one) and changes no
+ * result.  info may be NULL.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, fewer than 2 rows, no column, an ntext_bytes that is not rows x columns, a
+ * drawn column beyond the alignment, an unknown model, a max_dist that is not positive and finite, a distance that is not finite;
+ * CKM_ERANGE for more than 2^14 rows, more than 2^20 columns, more than 2^15 - 1 replicates or 2^15 matrices, a byte beyond ASCII.
+ * ckm_gtree_check applies the same tests and needs no device.  ckm_gtree_host is the host executor of gtree_dev.h behind the same
+ * arguments: the same bits as ckm_gtree_run, no device, for checks and comparisons (the times of its info stay 0). */
+typedef struct {
+  uint32_t nrows, ncols;   const uint8_t *text;   uint64_t ntext_bytes;
+  uint32_t nreps;          const uint32_t *cols;  uint32_t base;   int32_t model;   double max_dist;
+  const double *matrix;    uint32_t nmatrices;
+} ckm_gtree_args;
+typedef struct { uint32_t *compared, *differ;   double *dist;   uint32_t *merge_ij;   double *merge_len; } ckm_gtree_out;
+typedef struct {
+  uint64_t nrounds, ntrees, launches;
+  double   ms_upload, ms_gather, ms_counts, ms_dist, ms_joins, ms_download, ms_total;
+} ckm_gtree_info;
+int  ckm_gtree_check(const ckm_gtree_args *a);
+int  ckm_gtree_host(const ckm_gtree_args *a, uint64_t budget_bytes, const ckm_gtree_out *out, ckm_gtree_info *info);
+int  ckm_gtree_run(ckm_ctx *ctx, const ckm_gtree_args *a, uint64_t budget_bytes, const ckm_gtree_out *out, ckm_gtree_info *info);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
