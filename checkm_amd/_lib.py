@@ -316,7 +316,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
            "ckm_sim_check", "ckm_sim_run", "ckm_simscaf_check", "ckm_simscaf_run", "ckm_select_check", "ckm_select_run", "ckm_place_check", "ckm_place_run",
            "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free", "ckm_gtree_check", "ckm_gtree_host", "ckm_gtree_run",
-           "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_region"]
+           "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_envelope_paths", "ckm_debug_region"]
 
 _lib = None
 
@@ -472,6 +472,8 @@ def load():
                                     C.c_void_p, C.POINTER(C.c_uint32)]
     L.ckm_debug_envelopes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_uint32, C.c_void_p]
+    L.ckm_debug_envelope_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ckm_debug_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     if L.ckm_abi_version() != ABI_VERSION:
@@ -763,6 +765,24 @@ def debug_envelopes(ctx, profiles, seqs, model, seq, ienv, jenv):
     _chk(load().ckm_debug_envelopes(ctx.h, profiles.h, seqs.h, model.ctypes.data, seq.ctypes.data, ienv.ctypes.data,
                                     jenv.ctypes.data, len(model), out))
     return out
+
+
+def debug_envelope_paths(ctx, profiles, seqs, model, seq, ienv, jenv):
+    """The optimal-accuracy paths of chosen envelopes with their posterior lines: (ok[n], [int32[M] per envelope: the envelope-local
+    residue of every match node, 0 = none], [float32[Ld + 1] per envelope: the posterior of every residue on the path])."""
+    model = np.ascontiguousarray(model, dtype=np.uint32)
+    seq = np.ascontiguousarray(seq, dtype=np.uint32)
+    ienv = np.ascontiguousarray(ienv, dtype=np.int32)
+    jenv = np.ascontiguousarray(jenv, dtype=np.int32)
+    n = len(model)
+    off, ppo = np.zeros(n + 1, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([profiles.headers[int(m)]["leng"] for m in model], dtype=np.uint64)
+    ppo[1:] = np.cumsum(jenv.astype(np.int64) - ienv + 2, dtype=np.uint64)
+    ok = np.zeros(max(1, n), dtype=np.int32)
+    path, pp = np.zeros(max(1, int(off[-1])), dtype=np.int32), np.zeros(max(1, int(ppo[-1])), dtype=np.float32)
+    _chk(load().ckm_debug_envelope_paths(ctx.h, profiles.h, seqs.h, model.ctypes.data, seq.ctypes.data, ienv.ctypes.data, jenv.ctypes.data, n,
+                                         ok.ctypes.data, off.ctypes.data, path.ctypes.data, ppo.ctypes.data, pp.ctypes.data))
+    return ok[:n], [path[int(off[j]):int(off[j + 1])].copy() for j in range(n)], [pp[int(ppo[j]):int(ppo[j + 1])].copy() for j in range(n)]
 
 
 def debug_region(ctx, profiles, seqs, model, seq, ireg, jreg, cap=64):

@@ -381,6 +381,35 @@ extern "C" int ckm_debug_envelopes(ckm_ctx *ctx_, const ckm_profiles *p, const c
   });
 }
 
+// ckm_debug_envelopes with the OA paths and their posterior lines (rescore_envelopes with paths and pps: the items of
+// ckm_hits_write_alignments, whose posterior rows keep a matrix of their own).  out_off[n + 1] / node_residue: int32[M] per item, the
+// envelope-local residue of every match node; pp_off[n + 1] / pp: float[Ld + 1] per item.  Both stay zero where ok == 0.
+extern "C" int ckm_debug_envelope_paths(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_seqs *s, const uint32_t *model, const uint32_t *seq,
+                                        const int32_t *ienv, const int32_t *jenv, uint32_t n, int32_t *ok, const uint64_t *out_off,
+                                        int32_t *node_residue, const uint64_t *pp_off, float *pp) {
+  return guarded([&] {
+    if (!ctx_ || !p || !s || !model || !seq || !ienv || !jenv || !ok || !out_off || !node_residue || !pp_off || !pp) throw Error(CKM_EINVAL, "NULL argument");
+    ctx_->settle();
+    Worker *ctx = &ctx_->w[0];
+    HIPCHK(hipSetDevice(ctx->device));
+    std::vector<EnvReq> req(n); std::vector<EnvRes> res;
+    for (uint32_t i = 0; i < n; ++i) {
+      if (model[i] >= p->hmm.size() || seq[i] >= s->nseq || ienv[i] < 1 || jenv[i] > s->len[seq[i]] || jenv[i] < ienv[i]) throw Error(CKM_EINVAL, "bad envelope");
+      if (p->too_long[model[i]]) throw Error(CKM_ERANGE, "model longer than the instantiated kernel classes");
+      if (out_off[i + 1] - out_off[i] != (uint64_t)p->hmm[model[i]].M) throw Error(CKM_EINVAL, "out_off does not match the model lengths");
+      if (pp_off[i + 1] - pp_off[i] != (uint64_t)(jenv[i] - ienv[i] + 2)) throw Error(CKM_EINVAL, "pp_off does not match the envelope lengths");
+      req[i] = {model[i], seq[i], ienv[i], jenv[i]};
+    }
+    std::vector<std::vector<int32_t>> paths; std::vector<std::vector<float>> pps;
+    rescore_envelopes(ctx, p, s, req, res, &paths, &pps);
+    for (uint32_t i = 0; i < n; ++i) {
+      ok[i] = res[i].ok;
+      std::copy(paths[i].begin(), paths[i].end(), node_residue + out_off[i]);
+      std::copy(pps[i].begin(), pps[i].end(), pp + pp_off[i]);
+    }
+  });
+}
+
 extern "C" int ckm_debug_region(ckm_ctx *ctx_, const ckm_profiles *p, const ckm_seqs *s, uint32_t model, uint32_t seq, int32_t ireg, int32_t jreg,
                                 float *n2sum, int32_t *segs, int32_t *nseg, int32_t cap, int32_t *env, int32_t envcap, int32_t *nenv) {
   return guarded([&] {

@@ -1033,6 +1033,14 @@ typedef struct {
 int ckm_debug_envelopes(ckm_ctx *ctx, const ckm_profiles *p, const ckm_seqs *s,
                         const uint32_t *model, const uint32_t *seq, const int32_t *ienv, const int32_t *jenv,
                         uint32_t n, ckm_envelope_result *out);
+/* The same envelopes with their optimal-accuracy paths, as ckm_hits_write_alignments computes them: ok[n]; node_residue[out_off[i] ..
+ * out_off[i + 1]) = int32[M], the envelope-local residue (1-based) emitted by every match node of item i, 0 = none; pp[pp_off[i] ..
+ * pp_off[i + 1]) = float[Ld + 1], the posterior probability of every residue on the path in the state that emits it, 0 off the path.
+ * Both stay zero where ok == 0.  Additive: CKM_ABI_VERSION stays 12. */
+int ckm_debug_envelope_paths(ckm_ctx *ctx, const ckm_profiles *p, const ckm_seqs *s,
+                             const uint32_t *model, const uint32_t *seq, const int32_t *ienv, const int32_t *jenv,
+                             uint32_t n, int32_t *ok, const uint64_t *out_off, int32_t *node_residue,
+                             const uint64_t *pp_off, float *pp);
 
 /* The trace ensemble of one multi-domain region ireg..jreg (1-based, inclusive) of sequence `seq`:
  * n2sum[jreg-ireg+1] = per residue, sum over the 200 traces of the null2 odds ratio; segs[200*cap*4] / nseg[200] = every

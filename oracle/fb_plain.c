@@ -216,10 +216,14 @@ static void FN(upd)(double *gap, real best, real second) { if (second > -INFINIT
 /* Envelope rescoring of dsq[0..Ld-1] (the caller passes the envelope's residues and the unihit specials of the full length).
  * ppM, ppI [(Ld+1)*(M+1)]: work space, on return the posterior probabilities of the match and insert states (row 0 zero).
  * ppX [(Ld+1)*3]: N J C per residue.  null2[20].  coords[4] = hmm_from hmm_to ali_from ali_to, envelope-local (all 0 when no path).
- * out: [0] envsc  [1] Backward's total  [2] largest |sum of a residue's posteriors - 1|  [3] OA score  [4] runner-up gap of the trace.
+ * out: [0] envsc  [1] Backward's total  [2] largest |sum of a residue's posteriors - 1|  [3] OA score  [4] runner-up gap of the trace
+ *      [5] the posteriors the trace collects outside the core: C's of the residues behind the last match state, N's of those before the first.
+ * path [M+1]: the residue (envelope-local, 1-based) that match node k emits on the trace, 0 if none (index 0 unused).
+ * pp_path [Ld+1]: the posterior of residue i in the state that emits it on the trace (M or I), 0 off ali_from..ali_to.
  * lxe, lbt [Ld+1]: the log of the true xE of every Forward row, and of the largest true value (cells and specials) of every Backward row. */
 int FN(envelope)(int M, const real *bm, const real *t, const real *odds, const real *sp, const uint8_t *dsq, int Ld,
-                 real *ppM, real *ppI, real *ppX, double *null2, int32_t *coords, double *out, double *lxe, double *lbt)
+                 real *ppM, real *ppI, real *ppX, double *null2, int32_t *coords, double *out, double *lxe, double *lbt,
+                 int32_t *path, double *pp_path)
 {
   size_t W = (size_t)M + 1;
   real *xs = malloc(sizeof(real) * 5 * ((size_t)Ld + 1)); int32_t *ex = malloc(sizeof(int32_t) * 2 * ((size_t)Ld + 1)), *exc = ex + Ld + 1;
@@ -289,7 +293,8 @@ int FN(envelope)(int M, const real *bm, const real *t, const real *odds, const r
     oB[i] = MAX2(oN[i], oJ[i]);
   }
   out[3] = (double)oC[Ld];
-  double gap = INFINITY;
+  double gap = INFINITY, flank = 0;
+  memset(path, 0, sizeof(int32_t) * W); memset(pp_path, 0, sizeof(double) * R);
   int i = Ld, k = 0, st = 0, fi_ = 0, fk = 0, li = 0, lk = 0, done = 0;       /* st: 0 C, 1 E, 2 M, 3 I, 4 D */
   while (!done) {
     real *cm = oM + (size_t)i * W, *cd = oD + (size_t)i * W;
@@ -299,7 +304,7 @@ int FN(envelope)(int M, const real *bm, const real *t, const real *odds, const r
       if (i == 0) { done = 1; break; }
       real a = oC[i - 1] + ppX[(size_t)i * 3 + 2], e = oE[i];
       FN(upd)(&gap, MAX2(a, e), a > e ? e : a);
-      if (a >= e) i--; else st = 1;
+      if (a >= e) { flank += (double)ppX[(size_t)i * 3 + 2]; i--; } else st = 1;
     } break;
     case 1: {
       real second = -INFINITY; k = 0;
@@ -311,16 +316,18 @@ int FN(envelope)(int M, const real *bm, const real *t, const real *odds, const r
     } break;
     case 2: {
       fi_ = i; fk = k;
+      path[k] = i; pp_path[i] = (double)ppM[(size_t)i * W + k];
       real c[4] = { GATE(T(k - 1, MM), pm[k - 1]), GATE(T(k - 1, IM), pi[k - 1]), GATE(T(k - 1, DM), pd[k - 1]), GATE(bm[k], oB[i - 1]) };
       int best = 0; for (int q = 1; q < 4; q++) if (c[q] > c[best]) best = q;
       real second = -INFINITY; for (int q = 0; q < 4; q++) if (q != best && c[q] > second) second = c[q];
       FN(upd)(&gap, c[best], second);
       i--;
-      if (best == 3) done = 1; else { k--; st = best == 0 ? 2 : best == 1 ? 3 : 4; }
+      if (best == 3) { done = 1; for (int r = 1; r <= i; r++) flank += (double)ppX[(size_t)r * 3]; } else { k--; st = best == 0 ? 2 : best == 1 ? 3 : 4; }
     } break;
     case 3: {
       real a = GATE(T(k, MI), pm[k]), c = GATE(T(k, II), pi[k]);
       FN(upd)(&gap, MAX2(a, c), a > c ? c : a);
+      pp_path[i] = (double)ppI[(size_t)i * W + k];
       i--; st = a >= c ? 2 : 3;
     } break;
     case 4: {
@@ -333,7 +340,7 @@ int FN(envelope)(int M, const real *bm, const real *t, const real *odds, const r
 #undef GATE
 #undef MAX2
   coords[0] = fk; coords[1] = lk; coords[2] = fi_; coords[3] = li;
-  out[4] = gap;
+  out[4] = gap; out[5] = flank;
   free(oM); free(oN); free(xs); free(ex);
   return 0;
 }

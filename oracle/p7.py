@@ -109,7 +109,7 @@ def fb_plain():
         for sfx in ("_f64", "_f32", "_f80"):
             getattr(L, "fbp_forward" + sfx).argtypes = [I, P, P, P, P, P, I, P, P]
             getattr(L, "fbp_occupancy" + sfx).argtypes = [I, P, P, P, P, P, I, P, P, P, P]
-            getattr(L, "fbp_envelope" + sfx).argtypes = [I, P, P, P, P, P, I, P, P, P, P, P, P, P, P]
+            getattr(L, "fbp_envelope" + sfx).argtypes = [I, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P]
             getattr(L, "fbp_bias" + sfx).argtypes = [P, P, P, I, P]
         _fb = L
     return _fb

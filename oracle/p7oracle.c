@@ -803,8 +803,9 @@ static void null2_fill_degenerate(float *null2)
   null2[20] = null2[27] = null2[28] = 1.0f;
 }
 
-static int32_t *g_oa_path = NULL;    /* when set: receives, per model node (0-based), the envelope-local residue its match state emits (0 = none) */
-static float *g_oa_pp = NULL;        /* when set: receives, per envelope-local residue on the path, its posterior probability in the emitting state (M or I):
+/* (per thread: the host tests call p7o_envelope_alignment and p7o_align from a thread pool) */
+static _Thread_local int32_t *g_oa_path = NULL;    /* when set: receives, per model node (0-based), the envelope-local residue its match state emits (0 = none) */
+static _Thread_local float *g_oa_pp = NULL;        /* when set: receives, per envelope-local residue on the path, its posterior probability in the emitting state (M or I):
                                       * what hmmsearch's OA trace carries as tr->pp and prints as the PP line (p7_OATrace, p7_alidisplay_Create) */
 
 static int rescore_envelope(const PROF *p, const uint8_t *dsq_full, int L_full, int ienv, int jenv,
@@ -939,7 +940,7 @@ int p7o_envelope(const P7O_HMM *hmm, const uint8_t *dsq, int L_full, int ienv, i
 /* The alignment hmmsearch prints for a domain (hmmsearch without --noali: checkm/markerGeneFinder.py:138-142 under bKeepAlignment): the
  * optimal-accuracy path of the envelope ienv..jenv and the posterior probability of every residue on it.  path[k] (k = 0..M-1) = residue
  * (1-based within the envelope) emitted by match state k+1, 0 = none; pp[i] (i = 1..Ld, pp[0] unused) = posterior probability of residue i
- * in the state that emits it on the path, 0 off the path.  Not thread-safe (file-scope hooks into the traceback). */
+ * in the state that emits it on the path, 0 off the path.  (The hooks into the traceback are per thread.) */
 int p7o_envelope_alignment(const P7O_HMM *hmm, const uint8_t *dsq, int L_full, int ienv, int jenv, int32_t *path, float *pp)
 {
   PROF *p = prof_create(hmm); DOMAIN d;
@@ -956,7 +957,7 @@ int p7o_envelope_alignment(const P7O_HMM *hmm, const uint8_t *dsq, int L_full, i
  * length model of the sequence itself, Forward/Backward/decoding, optimal-accuracy alignment of the WHOLE sequence.  path[k]
  * (k = 0..M-1) = 1-based residue emitted by match state k+1, 0 if the node is deleted or outside the local alignment -- all
  * that HmmerAligner._maskAlignment keeps of the alignment (checkm/hmmerAligner.py:325-352: the '#=GC RF' x columns).
- * Not thread-safe (uses a file-scope hook into the traceback). */
+ * (The hook into the traceback is per thread.) */
 int p7o_align(const P7O_HMM *hmm, const uint8_t *dsq, int L, int32_t *path)
 {
   PROF *p = prof_create(hmm); DOMAIN d;

@@ -15,7 +15,8 @@ Forward   M(i,k) = odds_k(x_i) (B(i-1) BM_k + M(i-1,k-1) MM_{k-1} + I(i-1,k-1) I
 Backward  the same graph read from the end: C(L) = move, E(L) = C(L) EC, ...; its N(0) is the same total.
 Decoding  P(M_k emits i) = fM(i,k) bM(i,k) / Z; P(N emits i) = fN(i-1) loop bN(i) / Z, likewise J and C; the five sum to 1 per residue.
 null2     odds of residue x under the envelope's state usage: sum_k me[k] odds_k(x) + ie[k] + (xN + xJ + xC) / Ld.
-OA        the path of largest summed posterior over transitions of probability > 0; its score oC(Ld) and the trace's coordinates.
+OA        the path of largest summed posterior over transitions of probability > 0; its score oC(Ld), the trace's coordinates, the residue
+          of every match node on it and the posterior of every residue on it in the state that emits it (the alignment and its PP line).
 Regions   mocc(i) = 1 - P(N, J or C emits i), btot / etot the cumulated use of B and E; thresholds 0.25, 0.1, 0.2 as HMMER's
           p7_domaindef_ByPosteriorHeuristics applies them.
 Bias      Forward of the two-state model (background, model composition) as odds against the background, plus the length model.
@@ -246,7 +247,10 @@ def _specials_posterior(xs, ex, exc, xb, eb, ebn, i, loop, z, ez):
 
 def envelope_numpy(c, sp, dsq):
     """Forward, Backward, decoding, null2 and optimal accuracy of one envelope's residues: dict(envsc, btotal, ppM, ppI, ppX[Ld+1][3] = N J C,
-    null2[20], oasc, coords = (hmm_from, hmm_to, ali_from, ali_to) envelope-local, gap)."""
+    null2[20], oasc, coords = (hmm_from, hmm_to, ali_from, ali_to) envelope-local, gap, path[M+1] = the envelope-local residue match node k
+    emits on the trace (0: none), pp_path[Ld+1] = the posterior of residue i in the state that emits it on the trace (M or I; 0 off
+    ali_from..ali_to), flank = the posteriors the trace collects outside the core (C's behind the last match state, N's before the first):
+    sum(pp_path) + flank is oasc)."""
     M, dt, t, bm = c["M"], c["dtype"], c["t"], c["bm"]
     Ld = len(dsq)
     envsc, fM, fI, xs, ex, exc, _ = forward_numpy(c, sp, dsq)
@@ -291,6 +295,7 @@ def envelope_numpy(c, sp, dsq):
         if len(v) > 1 and v[1] > -np.inf:
             gap[0] = min(gap[0], v[0] - v[1])
     i, k, st, first, last = Ld, 0, "C", (0, 0), (0, 0)
+    path, pp_path, flank = np.zeros(M + 1, dtype=np.int32), np.zeros(Ld + 1), 0.0
     while True:
         if st == "C":
             if i == 0:
@@ -298,6 +303,7 @@ def envelope_numpy(c, sp, dsq):
             a, b = oC[i - 1] + ppX[i, 2], oE[i]
             upd([a, b])
             if a >= b:
+                flank += float(ppX[i, 2])
                 i -= 1
             else:
                 st = "E"
@@ -309,17 +315,20 @@ def envelope_numpy(c, sp, dsq):
             last, st = (i, k), "M"
         elif st == "M":
             first = (i, k)
+            path[k], pp_path[i] = i, float(ppM[i, k])
             cand = [oM[i - 1, k - 1] if t[k - 1, MM] > 0 else NEG, oI[i - 1, k - 1] if t[k - 1, IM] > 0 else NEG,
                     oD[i - 1, k - 1] if t[k - 1, DM] > 0 else NEG, oB[i - 1] if bm[k] > 0 else NEG]
             upd(cand)
             b = int(np.argmax(cand))
             i -= 1
             if b == 3:
+                flank += sum(float(v) for v in ppX[1:i + 1, 0])
                 break
             k, st = k - 1, "MID"[b]
         elif st == "I":
             a, b = (oM[i - 1, k] if t[k, MI] > 0 else NEG), (oI[i - 1, k] if t[k, II] > 0 else NEG)
             upd([a, b])
+            pp_path[i] = float(ppI[i, k])
             i, st = i - 1, ("M" if a >= b else "I")
         else:
             a, b = (oM[i, k - 1] if t[k - 1, MD] > 0 else NEG), (oD[i, k - 1] if t[k - 1, DD] > 0 else NEG)
@@ -328,7 +337,7 @@ def envelope_numpy(c, sp, dsq):
     with np.errstate(divide="ignore"):
         btotal = math.log(float(xb[0, 1])) + int(ebn[0]) * math.log(2.0)
     return dict(envsc=envsc, btotal=btotal, ppM=ppM, ppI=ppI, ppX=ppX, null2=null2, oasc=float(oC[Ld]),
-                coords=(first[1], last[1], first[0], last[0]), gap=gap[0])
+                coords=(first[1], last[1], first[0], last[0]), gap=gap[0], path=path, pp_path=pp_path, flank=flank)
 
 
 def occupancy_numpy(c, sp, dsq):
@@ -391,12 +400,14 @@ def envelope_c(c, sp, dsq, keep=False):
     d = np.ascontiguousarray(dsq, dtype=np.uint8)
     Ld, M, dt = len(d), c["M"], c["dtype"]
     ppM, ppI, ppX = np.zeros((Ld + 1, M + 1), dtype=dt), np.zeros((Ld + 1, M + 1), dtype=dt), np.zeros((Ld + 1, 3), dtype=dt)
-    null2, coords, out = np.zeros(20), np.zeros(4, dtype=np.int32), np.zeros(5)
+    null2, coords, out = np.zeros(20), np.zeros(4, dtype=np.int32), np.zeros(6)
     lxe, lbt = np.zeros(Ld + 1), np.zeros(Ld + 1)
+    path, pp_path = np.zeros(M + 1, dtype=np.int32), np.zeros(Ld + 1)
     getattr(p7.fb_plain(), "fbp_envelope" + _sfx(c))(*_model_args(c, sp), d.ctypes.data, Ld, ppM.ctypes.data, ppI.ctypes.data, ppX.ctypes.data,
-                                                     null2.ctypes.data, coords.ctypes.data, out.ctypes.data, lxe.ctypes.data, lbt.ctypes.data)
+                                                     null2.ctypes.data, coords.ctypes.data, out.ctypes.data, lxe.ctypes.data, lbt.ctypes.data,
+                                                     path.ctypes.data, pp_path.ctypes.data)
     r = dict(lxe=lxe, lbt=lbt, envsc=float(out[0]), btotal=float(out[1]), rowdev=float(out[2]), null2=null2, oasc=float(out[3]), coords=tuple(int(v) for v in coords),
-             gap=float(out[4]), ppX=ppX)
+             gap=float(out[4]), ppX=ppX, path=path, pp_path=pp_path, flank=float(out[5]))
     if keep:
         r["ppM"], r["ppI"] = ppM, ppI
     return r
@@ -482,6 +493,16 @@ def backward_overflow(lxe, lbt):
     return float(np.max(lbt - after)) - FLT_MAX_LOG
 
 
+def whole_overflow(model, dsq):
+    """backward_overflow of the unihit span (1, L) of a whole sequence against a Model: positive where an alignment of the sequence
+    (ckm_align, the oracle's p7o_align) must be refused.  The sequence must have a finite Forward score."""
+    L = len(dsq)
+    r = envelope_c(model.cfg(), specials(L, False), dsq)
+    if not consistent(r):
+        r = envelope_c(model.cfg(WIDE), specials(L, False, WIDE), dsq)
+    return backward_overflow(r["lxe"], r["lbt"])
+
+
 # ---- tolerances ---------------------------------------------------------------------------------------------------------------------
 # |got - ref64| <= K (Ld + 1) 2^-24 + 2 ulp32(|ref64|) nats for scores; |got / ref64 - 1| <= K_N2 (Ld + 1) 2^-24 for the null2 odds.
 # Each K is 4 x the largest ratio measure_tolerances() observes between the float32 and the float64 evaluation of the recurrences above
@@ -511,10 +532,19 @@ def backward_overflow(lxe, lbt):
 # would set the constant and leave 39 of 398 regions undecided.  Measured like the others (per residue and cumulated, float32 against
 # float64, 4 x, a power of two).
 #
+# K_PP is the constant of the posterior line of the OA path (pp_path: the posterior of every residue on the path in the state that emits
+# it), in K_REG's unit: |got - ref64| <= K_PP 2^-24 per residue.  A posterior lies in [0, 1] and is normalised by Z like mocc.  Measured
+# like the others over the decided envelopes (there both evaluations trace the same path, so the same cells are compared): the float32
+# error does grow with the envelope, but far slower than its length -- the largest per length class is 4 units at Ld < 32, 25 at
+# Ld = 32 .. 127, 67 at Ld = 512 .. 1023 and 177 at Ld = 3084 (M = 3073), about the square root of Ld.  In the unit (Ld + 1) 2^-24 the
+# largest ratio, 0.72, is set by an envelope of two residues and would give the constant 4: 9.8e-4 at Ld = 4100, sixteen times what
+# the flat unit allows there (1024 x 2^-24 = 6.1e-5), for a figure that is printed to one decimal.  So the flat unit was taken;
+# measure_tolerances() reports the other figure as pp_per_length.
+#
 # K_FWD's largest ratios come from the shortest targets against the long models (4.49 at M = 1024, L = 2): there the score is the log of
 # one row's sum over the entry distribution, and float32's occupancy recurrence and its sum over M nodes are what is being rounded.
-K_FWD, K_OA, K_BIAS, K_N2, K_GAP, K_REG = 32.0, 1024.0, 2.0, 128.0, 8.0, 1024.0
-OBSERVED = dict(fwd=4.494, oa=133.9, bias=0.4448, n2=30.09, gap=1.901, reg=206.8)      # the ratios measure_tolerances() gave when the constants were set
+K_FWD, K_OA, K_BIAS, K_N2, K_GAP, K_REG, K_PP = 32.0, 1024.0, 2.0, 128.0, 8.0, 1024.0, 1024.0
+OBSERVED = dict(fwd=4.494, oa=133.9, bias=0.4448, n2=30.09, gap=1.901, reg=206.8, pp=176.9)      # the ratios measure_tolerances() gave when the constants were set
 F32_CONSISTENT = 1e-3     # a float32 evaluation whose posteriors miss 1 by more than this left float32's range: it measures no rounding
 
 
@@ -534,6 +564,12 @@ def score_ratio(got, ref, Ld):
     if math.isinf(got) or math.isinf(ref):
         return 0.0 if got == ref else np.inf
     return max(0.0, abs(got - ref) - 2.0 * ulp32(ref)) / ((Ld + 1) * EPS32)
+
+
+def pp_ratio(got, ref):
+    """How many 2^-24 the posteriors along a path differ at most; inf for a NaN."""
+    d = np.abs(np.asarray(got, dtype=np.float64) - np.asarray(ref, dtype=np.float64))
+    return float(d.max()) / EPS32 if np.isfinite(d).all() else np.inf
 
 
 def n2_ratio(got, ref, Ld):
@@ -557,6 +593,7 @@ def launch_classes():
 TARGET_SEED = 83000
 RESEED = {4096: 1, 1: 1, 9: 1, 65: 1, 129: 1}             # models whose targets take another seed, chosen so that the reference alone meets the undecided caps
 GATED_M, GATED_NODE = 40, 20          # one more model of the first class: MD = 0 at this node, so the OA gates are exercised
+WHOLE_NAMES = ("planted", "two", "fragment", "nb_planted", "nb_fragment", "r1", "r17", "star_mid", "deg_allx", "star_only")   # the targets aligned as a whole (ckm_align)
 
 
 def class_of(M):
@@ -598,13 +635,30 @@ def own_targets(p):
     return recs
 
 
+ENSEMBLE_SEED = TARGET_SEED + 500000                      # the ensemble targets' generator: ENSEMBLE_SEED + M (+ 7 gated) + 100000 ENSEMBLE_RESEED[M]
+ENSEMBLE_RESEED = {}                                      # models whose ensemble target takes another seed, so that the oracle alone samples a trace of two segments in every class from 2 up
+
+
+def ensemble_target(p, gated=False):
+    """The text of a model's target for the trace ensemble: 6 random residues, three abutting pieces of the model -- its first 80 nodes, the
+    80 around its middle, its last 80 -- and 6 random residues.  About 250 residues at every M, so the region matrix stays small at
+    M = 4096, while both ends and the middle of the lane-striped row carry weight."""
+    M = p.M
+    rng = np.random.default_rng(ENSEMBLE_SEED + M + (7 if gated else 0) + 100000 * ENSEMBLE_RESEED.get(M, 0))
+    pieces = [synth.random_residues(rng, 6), synth.sample_domain(rng, p, 1, min(M, 80)), synth.sample_domain(rng, p, max(1, M // 2 - 40), min(M, M // 2 + 40)),
+              synth.sample_domain(rng, p, max(1, M - 79), M), synth.random_residues(rng, 6)]
+    return synth.to_text(np.concatenate(pieces))
+
+
 class Pair(object):
     __slots__ = ("M", "gated", "q", "name", "text", "dsq", "L", "fwd", "bias", "null", "nscale", "nscale_close", "regions", "tail", "btotal", "fwd32", "bias32", "occ_err")
 
 
 class Envelope(object):
     """ref: envelope_c's dictionary in float64 (in WIDE where float64 itself left its range: wide); f32: the same evaluation in float32,
-    in_range: whether that one hangs together; overflow, excused: backward_overflow and whether it is positive; undecided: the runner-up gap of the trace is below K_GAP's tolerance."""
+    in_range: whether that one hangs together; overflow, excused: backward_overflow and whether it is positive; undecided: the runner-up gap of the trace is below K_GAP's tolerance
+    (the gap is the smallest over every choice of the walk: a decided envelope has a decided whole path, ref["path"] and ref["pp_path"]).
+    An element of World.wholes that is no envelope of the world has no f32 (in_range is None), and ref is None where the target has no path."""
     __slots__ = ("M", "gated", "q", "name", "pair", "ienv", "jenv", "Ld", "ref", "wide", "f32", "in_range", "overflow", "excused", "undecided")
 
 
@@ -634,7 +688,12 @@ class World(object):
             self.pairs = list(ex.map(self._pair, sorted(jobs, key=lambda j: -j[0][0] * len(j[2]))))
             self.pairs.sort(key=lambda pr: order[((pr.M, pr.gated), pr.name)])
             self.envs = [e for pr in self.pairs for e in self._envelopes_of(pr)]
-            list(ex.map(self._envelope, sorted(self.envs, key=lambda e: -e.M * e.Ld)))
+            # ckm_align's reference: the unihit span (1, L) of every target of WHOLE_NAMES -- the world's own envelope where it has one
+            have = dict((id(e.pair), e) for e in self.envs if (e.ienv, e.jenv) == (1, e.pair.L))
+            self.wholes = [have.get(id(pr)) or self._span(pr, 1, pr.L) for pr in self.pairs if pr.name in WHOLE_NAMES]
+            more = [e for e in self.wholes if id(e.pair) not in have]
+            work = [(self._envelope, e) for e in self.envs] + [(self._whole, e) for e in more]
+            list(ex.map(lambda fe: fe[0](fe[1]), sorted(work, key=lambda fe: -fe[1].M * fe[1].Ld)))
 
     def _pair(self, job):
         (M, gated), name, text = job
@@ -661,27 +720,39 @@ class World(object):
         """The envelopes of a planted target: the reference's own single-domain regions, (1, L), (5, L - 3), (i, i) and (i, i + 1)."""
         if pr.name not in ("planted", "two", "noise3100"):
             return []
-        mid, out = pr.L // 2, []
-        for i, j in sorted(set([(i, j) for i, j, multi, _m in pr.regions if not multi] + [(1, pr.L), (5, pr.L - 3), (mid, mid), (mid, mid + 1)])):
-            e = Envelope()
-            e.M, e.gated, e.q, e.name, e.pair, e.ienv, e.jenv, e.Ld = pr.M, pr.gated, pr.q, pr.name, pr, i, j, j - i + 1
-            out.append(e)
-        return out
+        mid = pr.L // 2
+        spans = sorted(set([(i, j) for i, j, multi, _m in pr.regions if not multi] + [(1, pr.L), (5, pr.L - 3), (mid, mid), (mid, mid + 1)]))
+        return [World._span(pr, i, j) for i, j in spans]
 
-    def _envelope(self, e):
+    @staticmethod
+    def _span(pr, i, j):
+        e = Envelope()
+        e.M, e.gated, e.q, e.name, e.pair, e.ienv, e.jenv, e.Ld = pr.M, pr.gated, pr.q, pr.name, pr, i, j, j - i + 1
+        return e
+
+    def _envelope(self, e, with_f32=True):
         _i, model = self.model_of(e)
         L, dsq = e.pair.L, e.pair.dsq[e.ienv - 1:e.jenv]
         e.ref = envelope_c(model.cfg(), specials(L, False), dsq)
         e.wide = not consistent(e.ref)
         if e.wide:
             e.ref = envelope_c(model.cfg(WIDE), specials(L, False, WIDE), dsq)
-        e.f32 = envelope_c(model.cfg(np.float32), specials(L, False, np.float32), dsq)
+        e.f32 = envelope_c(model.cfg(np.float32), specials(L, False, np.float32), dsq) if with_f32 else None
         e.overflow = backward_overflow(e.ref["lxe"], e.ref["lbt"])
         e.excused = e.overflow > 0
         for r in (e.f32, e.ref):
-            del r["ppX"], r["lxe"], r["lbt"]
-        e.in_range = consistent(e.f32, F32_CONSISTENT)
+            if r is not None:
+                del r["ppX"], r["lxe"], r["lbt"]
+        e.in_range = consistent(e.f32, F32_CONSISTENT) if with_f32 else None
         e.undecided = e.ref["gap"] < K_GAP * (e.Ld + 1) * EPS32
+
+    def _whole(self, e):
+        """The span (1, L) of a target that is aligned as a whole and is no envelope of the world: the float64 evaluation alone (nothing is
+        measured on it), and nothing at all where no path exists (the Forward total is 0: ref is None)."""
+        if math.isfinite(e.pair.fwd):
+            self._envelope(e, with_f32=False)
+        else:
+            e.ref, e.wide, e.f32, e.overflow, e.excused, e.in_range, e.undecided = None, False, None, -np.inf, False, None, False
 
     @classmethod
     def get(cls):
@@ -731,17 +802,47 @@ def envelope_findings(e, rc_ok, envsc, oasc, null2, coords, who):
     return bad if rc_ok else [tag + ("ok", 0, 1, e.overflow)]
 
 
+def path_findings(e, rc_ok, path, pp, who):
+    """(the failures of one envelope's alignment against the reference, the pp ratio or None where nothing was compared): path = int32[M],
+    the envelope-local residue of match node k at k - 1, pp = float[Ld + 1].  Refused exactly where excused; where the envelope is decided,
+    the path node for node, pp within K_PP 2^-24 and exactly 0 off ali_from..ali_to.  An undecided envelope's path is not compared."""
+    tag = (who, e.M, "gated" if e.gated else e.q, e.name, e.ienv, e.jenv)
+    if e.excused or not rc_ok:
+        return ([] if e.excused != bool(rc_ok) else [tag + ("ok", int(bool(rc_ok)), int(not e.excused), e.overflow)]), None
+    if e.undecided:
+        return [], None
+    r, bad = e.ref, []
+    path, pp = np.asarray(path), np.asarray(pp, dtype=np.float64)
+    differ = np.nonzero(path != r["path"][1:])[0]
+    if len(differ):
+        k = int(differ[0])
+        bad.append(tag + ("path", "%d nodes differ, the first is node" % len(differ), k + 1, int(path[k]), int(r["path"][k + 1])))
+    ratio = pp_ratio(pp, r["pp_path"])
+    if not ratio <= K_PP:
+        i = int(np.argmax(np.abs(pp - r["pp_path"])))
+        bad.append(tag + ("pp", "residue", i, float(pp[i]), float(r["pp_path"][i]), ratio))
+    outside = np.ones(e.Ld + 1, dtype=bool)
+    outside[r["coords"][2]:r["coords"][3] + 1] = False
+    if np.any(pp[outside] != 0):
+        bad.append(tag + ("pp off the alignment", int(np.nonzero(outside & (pp != 0))[0][0])))
+    return bad, ratio
+
+
 def measure_tolerances(world):
     """The largest ratio of |float32 evaluation - float64 evaluation| to its unit, per quantity, over every pair and every envelope of the
-    world that is not excused (backward_overflow): dict(fwd, oa, bias, n2, gap, reg, left_out).  fwd covers the whole-sequence Forward and envsc;
-    gap is taken where both evaluations trace the same path (the host test asserts that they do wherever the envelope is decided)."""
+    world that is not excused (backward_overflow): dict(fwd, oa, bias, n2, gap, reg, pp, pp_per_length, left_out).  fwd covers the whole-sequence
+    Forward and envsc; gap is taken where both evaluations trace the same path (the host test asserts that they do wherever the envelope is
+    decided); pp, in units of 2^-24, over the decided envelopes (the same path: the same cells are compared), pp_per_length the same figure
+    in units of (Ld + 1) 2^-24 -- the unit that was not taken, see K_PP."""
     ins = [e for e in world.envs if not e.excused]
     return dict(fwd=max([score_ratio(pr.fwd32, pr.fwd, pr.L) for pr in world.pairs] + [score_ratio(np.float32(e.f32["envsc"]), e.ref["envsc"], e.Ld) for e in ins]),
                 bias=max(score_ratio(pr.bias32, pr.bias, pr.L) for pr in world.pairs),
                 oa=max(score_ratio(np.float32(e.f32["oasc"]), e.ref["oasc"], e.Ld) for e in ins),
                 n2=max(n2_ratio(e.f32["null2"], e.ref["null2"], e.Ld) for e in ins),
                 gap=max(abs(e.f32["gap"] - e.ref["gap"]) / ((e.Ld + 1) * EPS32) for e in ins if e.f32["coords"] == e.ref["coords"] and math.isfinite(e.ref["gap"])),
-                reg=max(pr.occ_err for pr in world.pairs) / EPS32, left_out=[e for e in world.envs if e.excused])
+                reg=max(pr.occ_err for pr in world.pairs) / EPS32, left_out=[e for e in world.envs if e.excused],
+                pp=max(pp_ratio(e.f32["pp_path"], e.ref["pp_path"]) for e in ins if e.in_range and not e.undecided),
+                pp_per_length=max(pp_ratio(e.f32["pp_path"], e.ref["pp_path"]) / (e.Ld + 1) for e in ins if e.in_range and not e.undecided))
 
 
 def k_of(ratio):

@@ -51,6 +51,8 @@ def _numpy_vs_c(c, L_full, dsq, label):
                 bad.append((label, k, n[k] if np.ndim(n[k]) == 0 else None, r[k] if np.ndim(r[k]) == 0 else None))
         if n["coords"] != r["coords"] or not _close(n["gap"], r["gap"], 1e-9):
             bad.append((label, "trace", n["coords"], r["coords"], n["gap"], r["gap"]))
+        if not np.array_equal(n["path"], r["path"]) or not _close(n["pp_path"], r["pp_path"]) or not _close(n["flank"], r["flank"]):
+            bad.append((label, "path", n["path"], r["path"], n["flank"], r["flank"]))
     if not _close(fb.bias_numpy(c, dsq), fb.bias_c(c, dsq), 1e-12 if c["dtype"] is not np.float32 else 1e-6):
         bad.append((label, "bias"))
     return bad
@@ -85,7 +87,32 @@ def test_reference_invariants(world):
             bad.append((e.M, e.name, e.ienv, e.jenv, "oasc > Ld", r["oasc"]))
         if e.wide and e.in_range:
             bad.append((e.M, e.name, e.ienv, e.jenv, "float64 left its range where float32 did not"))
+    # the trace: what the walk returns besides its four end coordinates
+    paths = 0
+    for e in world.envs + [w for w in world.wholes if w.ref is not None and w not in world.envs]:
+        r, tag = e.ref, (e.M, e.name, e.ienv, e.jenv)
+        path, pp = r["path"], r["pp_path"]
+        assert path.shape == (e.M + 1,) and pp.shape == (e.Ld + 1,) and path[0] == 0 and pp[0] == 0
+        nodes = np.nonzero(path)[0]
+        if len(nodes) == 0:
+            if r["coords"] != (0, 0, 0, 0) or pp.any():
+                bad.append(tag + ("no path, but coordinates or posteriors", r["coords"]))
+            continue
+        paths += 1
+        if not np.all(np.diff(path[nodes]) > 0):
+            bad.append(tag + ("residues along the path do not increase",))
+        if (int(nodes[0]), int(nodes[-1]), int(path[nodes[0]]), int(path[nodes[-1]])) != r["coords"]:
+            bad.append(tag + ("ends of the path", (int(nodes[0]), int(nodes[-1]), int(path[nodes[0]]), int(path[nodes[-1]])), r["coords"]))
+        total = float(pp.sum()) + r["flank"]
+        if not abs(total - r["oasc"]) <= 1e-9 * max(1.0, abs(r["oasc"])):
+            bad.append(tag + ("sum of the path's posteriors and the flanks is not oasc", total, r["oasc"]))
+        if not (np.all(pp >= 0) and np.all(pp <= 1 + 1e-12)):
+            bad.append(tag + ("a posterior outside [0, 1]", float(pp.min()), float(pp.max())))
+        a, b = r["coords"][2], r["coords"][3]
+        if pp[:a].any() or pp[b + 1:].any() or not np.all(pp[a:b + 1] > 0):
+            bad.append(tag + ("posteriors off the alignment, or none on it",))
     assert not bad, bad[:10]
+    assert paths >= len(world.envs)
 
 
 def test_world_coverage_and_undecided_caps(world):
@@ -115,12 +142,13 @@ def test_world_coverage_and_undecided_caps(world):
 def test_tolerance_constants_are_the_measured_ones(world):
     got = fb.measure_tolerances(world)
     print("measured ratios", dict((k, v) for k, v in got.items() if k != "left_out"), "left out", len(got["left_out"]))
-    for k, K in (("fwd", fb.K_FWD), ("oa", fb.K_OA), ("bias", fb.K_BIAS), ("n2", fb.K_N2), ("gap", fb.K_GAP), ("reg", fb.K_REG)):
+    for k, K in (("fwd", fb.K_FWD), ("oa", fb.K_OA), ("bias", fb.K_BIAS), ("n2", fb.K_N2), ("gap", fb.K_GAP), ("reg", fb.K_REG), ("pp", fb.K_PP)):
         assert got[k] <= K / 4.0, (k, got[k], K)
         assert fb.k_of(fb.OBSERVED[k]) == K, (k, fb.OBSERVED[k], K)
     assert fb.K_GAP < fb.K_OA
-    differ = [(e.M, e.name, e.ienv, e.jenv) for e in world.envs if e.in_range and not e.undecided and e.f32["coords"] != e.ref["coords"]]
-    assert not differ, differ                      # a decided envelope's trace is the same in float32
+    differ = [(e.M, e.name, e.ienv, e.jenv) for e in world.envs if e.in_range and not e.undecided and
+              (e.f32["coords"] != e.ref["coords"] or not np.array_equal(e.f32["path"], e.ref["path"]))]
+    assert not differ, differ                      # a decided envelope's trace is the same in float32, node for node
     # what is excused is what the constants' comment says, by the exact condition, well away from its limit; and the float32 evaluation
     # hangs together on exactly the others
     assert all(e.name == "two" and e.M >= 192 and (e.ienv, e.jenv) in ((1, e.pair.L), (5, e.pair.L - 3)) for e in got["left_out"])
@@ -155,6 +183,41 @@ def test_oracle_within_tolerance(world, hs):
                 worst[f] = max(worst[f], ratio)
     print("largest oracle-to-reference ratios", dict(worst))
     assert not bad, bad[:10]
+
+
+def test_oracle_alignments(world, hs):
+    """p7o_envelope_alignment on every envelope of the world and p7o_align on every target that is aligned as a whole: refused exactly
+    where excused, the path of a decided envelope node for node, its posterior line within K_PP and 0 off the alignment."""
+    def env(e):
+        return hs.envelope_alignment(world.model_of(e)[0], e.pair.dsq, e.ienv, e.jenv)
+
+    def whole(e):
+        return hs.align(world.model_of(e)[0], e.pair.dsq)
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        envs = list(ex.map(env, world.envs))
+        wholes = list(ex.map(whole, world.wholes))
+    bad, worst, checked = [], 0.0, collections.Counter()
+    for e, (rc, path, pp) in zip(world.envs, envs):
+        b, ratio = fb.path_findings(e, rc == 0, path, pp, "oracle")
+        bad += b
+        if ratio is not None:
+            worst, checked[e.q] = max(worst, ratio), checked[e.q] + 1
+    decided = collections.Counter()
+    for e, (rc, path) in zip(world.wholes, wholes):
+        tag = ("oracle align", e.M, "gated" if e.gated else e.q, e.name)
+        if e.ref is None or e.excused:                       # no path at all (the Forward total is 0), or float32 cannot hold Backward
+            if rc == 0 or path.any():
+                bad.append(tag + ("answered", rc))
+        elif rc != 0:
+            bad.append(tag + ("refused", rc, e.overflow))
+        elif not e.undecided:
+            decided[e.q] += 1
+            if not np.array_equal(path, e.ref["path"][1:]):
+                k = int(np.nonzero(path != e.ref["path"][1:])[0][0])
+                bad.append(tag + ("node", k + 1, int(path[k]), int(e.ref["path"][k + 1])))
+    print("largest oracle-to-reference pp ratio", worst, "paths checked", dict(checked), "whole sequences", dict(decided))
+    assert not bad, bad[:10]
+    assert all(checked[q] >= 3 and decided[q] >= 3 for q in fb.KFB_Q), (dict(checked), dict(decided))
 
 
 def test_oracle_regions_from_search(world, hs):

@@ -1,6 +1,7 @@
 """End to end through the reference's own API surface: MarkerGeneFinder.find -> ResultsParser.analyseResults
 -> printSummary, on the GPU, against (scan oracle -> domtblout text -> reduce oracle)."""
 import os
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -13,6 +14,7 @@ from checkm_amd.resultsParser import ResultsParser
 from oracle import p7
 from oracle import reduce_oracle as ro
 from tests import common
+from tests import fb_reference as fb
 
 pytestmark = pytest.mark.gpu
 
@@ -153,16 +155,25 @@ def test_align_matches_the_oracle(gpu_ctx):
     seqs = _lib.Seqs(gpu_ctx, [recs])
     hs = p7.HmmSet(path)
     got = _lib.align(gpu_ctx, prof, seqs, model, list(range(len(recs))))
-    nmatched = 0
+    # where no column may be reported: the float64 reference's exact condition (a float32 Backward scaled by Forward's factors must hold a
+    # value above float32's largest number: two strong copies under a one-domain model), from the HMM text
+    models = [fb.Model(r) for r in fb.parse_hmm(open(path).read())]
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        overflow = list(ex.map(lambda rm: fb.whole_overflow(models[rm[1]], p7.digitize(rm[0][2])), zip(recs, model)))
+    nmatched, nrefused = 0, 0
     for r, (rec, m) in enumerate(zip(recs, model)):
         rc, want = hs.align(m, p7.digitize(rec[2]))
         assert len(got[r]) == profs[m].M
-        if rc != 0:        # posterior decoding left the float range (two strong copies under a one-domain model): no column is reported
-            assert rec[0].endswith("_3") and (got[r] == 0).all(), rec[0]
+        # (no pair may sit on the limit itself: the value float32 holds is the true one to about Ld rounding errors, 1e-4 nats at these lengths)
+        assert (rc != 0) == (overflow[r] > 0) and abs(overflow[r]) > 1e-3, (rec[0], rc, overflow[r])
+        if overflow[r] > 0:
+            assert (got[r] == 0).all(), rec[0]
+            nrefused += 1
             continue
         assert (got[r] == want).all(), (rec[0], np.nonzero(got[r] != want)[0][:5])
         nmatched += int((want > 0).sum())
     assert nmatched > 0.5 * sum(profs[m].M for m in model[::4])
+    assert nrefused >= 1 and nrefused < len(profs)          # some two-copy targets are refused, and not all of them
     prof.close(); seqs.close(); hs.close()
 
 
