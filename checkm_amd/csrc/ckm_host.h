@@ -24,6 +24,7 @@
 #include "dev_types.h"
 #include "host_pool.h"
 #include "stream_plan.h"
+#include "cascade_plan.h"
 
 namespace ckm {
 
@@ -281,9 +282,7 @@ struct Worker {
   size_t ws_budget = (size_t)8 << 30;     // float workspace budget (bytes) for Forward/Backward matrices
   std::unique_ptr<HostPool> pool;         // host threads of this worker
   // ---- device-driven cascade (ckm_cascade.hip): tables, queues and result buffers of this lane; capacities only grow ----
-  struct CascadeCaps { uint32_t fwork = 0, ework = 0, rwork = 0, pass = 0, reg = 0, events_f = 0, events_e = 0, seen_rwork = 0; uint64_t hens = 0;
-                       uint32_t div_cand = 12, div_nores = 48, div_fwork = 160, div_ework = 256, div_rwork = 32768;        // per-group tables hold max(pairs / div, floor) entries
-                       uint32_t fl_cand = 4096, fl_nores = 2048, fl_fwork = 2048, fl_ework = 1024, fl_rwork = 256; float ws_per_cell = 11.f, z1_per_pair = 64.f; } caps;      // (z1_per_pair: bytes of workspace zone 1 per pair; like ws_per_cell it only grows, to 1.15 x what a search that overflowed asked for)
+  CascadeCaps caps;                       // (cascade_plan.h)
   DevBuf c_cnt, c_cand, c_nores, c_bias, c_vfast, c_vexact, c_vflag, c_route, c_vq, c_vxq, c_fq, c_bq, c_eq, c_rq, c_fwork, c_ework, c_rwork, c_ens, c_ensq,
          c_fout_f, c_fout_e, c_fout_r, c_rerr_e, c_rerr_r, c_tops, c_events_r, c_pass, c_reg, c_hens, c_envout, c_events_f, c_events_e;
   PinnedBuf h_cnt, h_pass, h_reg, h_envout, h_events_f, h_events_e, h_hens, h_tops;
@@ -302,7 +301,6 @@ struct Worker {
 constexpr int kVitQH[ckm::NVW] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16, 24, 32};
 constexpr int kVit16Q[ckm::NV16] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16};
 constexpr int kFbQ[ckm::NFC] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 48, 64};
-constexpr int kSsvNone = 65;          // "SSV class" of a model beyond the 2048 nodes the SSV kernel's LDS image holds: every pair goes to the exact MSV kernel
 inline int vit_class_id(int QH) { for (int i = 0; i < ckm::NVW; ++i) if (kVitQH[i] == QH) return ckm::NV16 + i; return -1; }
 inline int vit16_class_id(int Q16) { for (int i = 0; i < ckm::NV16; ++i) if (kVit16Q[i] == Q16) return i; return -1; }
 inline int fb_class_id(int Q) { for (int i = 0; i < ckm::NFC; ++i) if (kFbQ[i] == Q) return i; return -1; }

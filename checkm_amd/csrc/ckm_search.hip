@@ -84,9 +84,31 @@ void assemble_hits(Worker *ctx, const ckm_profiles *p, const ckm_seqs *s, DomSta
   for (size_t q = 0; q < ds.pass.size(); ++q) if (has_hit[q]) by_bin_model[{s->seq_bin[hit_of[q].seq], hit_of[q].model}].push_back(std::move(hit_of[q]));
 }
 
-// The whole filter cascade + domain stage for a subset of the models, on one worker.
-struct SeqRange { std::vector<uint32_t> lo, hi; std::vector<uint64_t> res; uint64_t tag = 0; };   // per bin: [lo, hi) of s->order, residues in it
+// The lanes of a search take their SSV phases in turn (ckm_ctx::ssv_turn).
+struct TurnGuard {      // a worker that never reaches an SSV phase (no pairs, or an error) still passes the turn on
+  ckm_ctx *o; int t; bool *took;
+  ~TurnGuard() { if (*took) return; std::unique_lock<std::mutex> l(o->ssv_mutex); o->ssv_cv.wait(l, [&] { return o->ssv_turn == t; }); o->ssv_turn++; o->ssv_cv.notify_all(); }
+};
 
+// What cascade_plan.h takes from the environment and from the models, once per call (tests and bench.py change the variables between calls)
+static PlanOptions plan_options() {
+  PlanOptions o;
+  if (const char *e = getenv("CKM_PAIR_BUDGET")) o.pair_budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+  if (const char *e = getenv("CKM_SPLIT_MIN_PAIRS")) o.split_min = strtoull(e, nullptr, 10);
+  o.long_share = getenv("CKM_LONG_SHARE");
+  if (const char *e = getenv("CKM_CAP_SHRINK")) o.shrink = (uint64_t)std::max(1, atoi(e));
+  return o;
+}
+static std::vector<PlanModel> plan_models(const ckm_profiles *p, const std::vector<uint32_t> &my_models) {
+  std::vector<PlanModel> pm(p->prof.size());
+  for (uint32_t m : my_models) {
+    const int cls = ssv_class(p->prof[m]);
+    pm[m] = PlanModel{cls, ssv_per_block(cls), p->prof[m].M, p->prof[m].fbQ, p->dm[m].vit_cls, p->dm[m].vitx_cls, p->dm[m].fb_cls};
+  }
+  return pm;
+}
+
+// The whole filter cascade + domain stage for a subset of the models, on one worker.
 static void cascade(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profiles *p, const ckm_seqs *s, const SeqRange &rng, const std::vector<uint32_t> &my_models,
                     const std::vector<std::vector<uint32_t>> &model_bins, HitMap &by_bin_model, bool turn_done = false) {
   HIPCHK(hipSetDevice(ctx->device));
@@ -102,72 +124,36 @@ static void cascade(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profiles
   // ---- stage 1: SSV over every pair, chunked by a pair budget ----
   std::vector<Cand> cands;
   bool took_turn = turn_done;          // (the lane's turn was already taken and passed on by the device-driven attempt this call replaces)
-  struct TurnGuard {      // a worker that never reaches an SSV phase (no pairs, or an error) still passes the turn on
-    ckm_ctx *o; int t; bool *took;
-    ~TurnGuard() { if (*took) return; std::unique_lock<std::mutex> l(o->ssv_mutex); o->ssv_cv.wait(l, [&] { return o->ssv_turn == t; }); o->ssv_turn++; o->ssv_cv.notify_all(); }
-  } turn_guard{owner, my_turn, &took_turn};
+  TurnGuard turn_guard{owner, my_turn, &took_turn};
   {
-    uint64_t pair_budget = (uint64_t)1 << 29;                  // pairs per SSV chunk (2 B of maxV each); CKM_PAIR_BUDGET overrides (tests)
-    if (const char *e = getenv("CKM_PAIR_BUDGET")) pair_budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
+    const uint64_t pair_budget = plan_options().pair_budget;      // (of the options this cascade uses the budget alone: it has no parts and no per-group tables)
+    const std::vector<PlanModel> pm = plan_models(p, my_models);
     size_t i0 = 0;
     while (i0 < my_models.size()) {
       // gather models of this chunk
-      struct MW { uint32_t model; uint64_t pair_base; uint64_t npairs; };
       const bool i0_was_first = (i0 == 0);
-      std::vector<MW> mws; uint64_t npairs = 0; size_t i1 = i0;
-      for (; i1 < my_models.size(); ++i1) {
-        const uint32_t m1 = my_models[i1];
-        uint64_t n = 0;
-        for (uint32_t b : model_bins[m1]) n += rng.hi[b] - rng.lo[b];
-        if (n == 0) continue;
-        if (npairs + n > pair_budget && !mws.empty()) break;
-        mws.push_back({m1, npairs, n}); npairs += n;
-      }
-      i0 = i1;
+      const LaneModels chunk = lane_models(rng, my_models, model_bins, i0, pair_budget);
+      const std::vector<MW> &mws = chunk.mws; const uint64_t npairs = chunk.total_pairs;
+      i0 = chunk.next;
       if (mws.empty() || npairs == 0) continue;
       std::unique_lock<std::mutex> ssv_lock(owner->ssv_mutex);     // one SSV phase at a time (VALU-bound); released after the finish kernel
       if (!took_turn) owner->ssv_cv.wait(ssv_lock, [&] { return owner->ssv_turn == my_turn; });
       CKM_TRACE_PT("ssv turn taken");
-      // The block table depends only on (profiles, sequences, models and their bins): reuse the resident one when the
-      // previous call on this worker had the same plan (lineage_wf scans the same bins twice; bench repeats steps).
-      std::vector<uint64_t> key{p->uid, s->uid, pair_budget, (uint64_t)i0, rng.tag};
-      for (auto &mw : mws) { key.push_back(0xffffffffull + mw.model); for (uint32_t b : model_bins[mw.model]) key.push_back(b); }
-      std::vector<std::pair<int, std::pair<size_t, size_t>>> groups;
-      size_t nblocks_total = 0;
-      const bool single_chunk = (i1 == my_models.size() && i0_was_first);
+      std::vector<uint64_t> key = plan_key_host(p->uid, s->uid, pair_budget, (uint64_t)i0, rng.tag, mws, model_bins);
+      PlanGroups groups;
+      const bool single_chunk = (i0 == my_models.size() && i0_was_first);
       if (single_chunk && key == ctx->plan_key) {
-        groups = ctx->plan_groups; nblocks_total = ctx->plan_nblocks;
+        groups = ctx->plan_groups;
         st.pairs_ssv += ctx->plan_pairs; st.residue_hmm += ctx->plan_residue_hmm; st.cells_ssv += ctx->plan_cells;
       } else {
-        std::map<int, std::vector<SsvBlockWork>> byQ;
-        uint64_t c_pairs = 0, c_res = 0, c_cells = 0;
-        for (auto &mw : mws) {
-          const int Q = ssv_class(p->prof[mw.model]); const uint32_t per_block = ssv_per_block(Q);
-          uint64_t pb = mw.pair_base;
-          for (uint32_t b : model_bins[mw.model]) {
-            const uint32_t o0 = rng.lo[b], n = rng.hi[b] - o0;
-            for (uint32_t a = 0; a < n; a += per_block) {
-              SsvBlockWork w; w.model = mw.model; w.list_start = o0 + a; w.count = std::min(per_block, n - a); w.pair_start = (uint32_t)(pb + a);
-              byQ[Q].push_back(w);
-            }
-            pb += n; c_res += rng.res[b]; c_cells += rng.res[b] * (uint64_t)p->prof[mw.model].M;
-          }
-          c_pairs += mw.npairs;
-        }
-        st.pairs_ssv += c_pairs; st.residue_hmm += c_res; st.cells_ssv += c_cells;
-        std::vector<SsvBlockWork> allw;
-        for (auto &kv : byQ) {
-          // longest blocks first inside a launch (a block's time is set by its first = longest sequence): without this
-          // the few very long sequences of each bin start late and leave most CUs idle at the end of every launch
-          std::stable_sort(kv.second.begin(), kv.second.end(), [&](const SsvBlockWork &x, const SsvBlockWork &y) {
-            return s->len[s->order[x.list_start]] > s->len[s->order[y.list_start]]; });
-          groups.push_back({kv.first, {allw.size(), kv.second.size()}}); allw.insert(allw.end(), kv.second.begin(), kv.second.end());
-        }
-        nblocks_total = allw.size();
+        BlockTable bt = block_table_host(mws, pm.data(), model_bins, rng, s->order.data(), s->len.data());
+        st.pairs_ssv += bt.pairs; st.residue_hmm += bt.residues; st.cells_ssv += bt.cells;
+        groups = std::move(bt.groups);
+        const std::vector<SsvBlockWork> &allw = bt.work;
         ctx->work.ensure(allw.size() * sizeof(SsvBlockWork));
         HIPCHK(hipMemcpyAsync(ctx->work.p, allw.data(), allw.size() * sizeof(SsvBlockWork), hipMemcpyHostToDevice, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));            // allw goes out of scope
-        if (single_chunk) { ctx->plan_key = key; ctx->plan_groups = groups; ctx->plan_nblocks = nblocks_total; ctx->plan_pairs = c_pairs; ctx->plan_residue_hmm = c_res; ctx->plan_cells = c_cells; }
+        if (single_chunk) { ctx->plan_key = std::move(key); ctx->plan_groups = groups; ctx->plan_nblocks = allw.size(); ctx->plan_pairs = bt.pairs; ctx->plan_residue_hmm = bt.residues; ctx->plan_cells = bt.cells; }
         else ctx->plan_key.clear();
       }
       uint32_t cap_surv = (uint32_t)std::max<uint64_t>(1 << 16, npairs / 8), cap_nores = (uint32_t)std::max<uint64_t>(1 << 14, npairs / 64);
@@ -516,225 +502,55 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   const uint64_t *off = s->d_off.as<uint64_t>();
   const int32_t *dlen = s->d_len.as<int32_t>();
   bool took_turn = false;
-  struct TurnGuard {
-    ckm_ctx *o; int t; bool *took;
-    ~TurnGuard() { if (*took) return; std::unique_lock<std::mutex> l(o->ssv_mutex); o->ssv_cv.wait(l, [&] { return o->ssv_turn == t; }); o->ssv_turn++; o->ssv_cv.notify_all(); }
-  } turn_guard{owner, my_turn, &took_turn};
+  TurnGuard turn_guard{owner, my_turn, &took_turn};
 
-  // ---- the lane's pairs; a search with more pairs than the SSV budget goes through the host-driven cascade (it works chunk by chunk) ----
-  uint64_t pair_budget = (uint64_t)1 << 29;
-  if (const char *e = getenv("CKM_PAIR_BUDGET")) pair_budget = std::max<uint64_t>(1, strtoull(e, nullptr, 10));
-  struct MW { uint32_t model; uint64_t pair_base; uint64_t npairs; };
-  std::vector<MW> mws;
-  uint64_t total_pairs = 0;
-  for (uint32_t m1 : my_models) {
-    uint64_t n = 0;
-    for (uint32_t b : model_bins[m1]) n += rng.hi[b] - rng.lo[b];
-    if (n == 0) continue;
-    mws.push_back({m1, total_pairs, n}); total_pairs += n;
-  }
-  if (total_pairs == 0) { st.ms_total = now_ms() - t_start; return 0; }
-  if (total_pairs > pair_budget) return 2;
-
-  // ---- SSV block table, grouped by SSV register class = model length class (cached when the previous call on this worker had the same
-  // plan: lineage_wf scans the same bins twice, bench repeats steps).  Each group is one SSV launch AND one sub-cascade: its survivors
-  // go down their own chain of queues as soon as that launch is done, while the SSV launches of the other groups still run. ----
+  // ---- the plan (cascade_plan.h): the lane's pairs, the parts by sequence length, the SSV block table and its groups, the groups' demands ----
+  const PlanOptions opt = plan_options();
+  const std::vector<PlanModel> pm = plan_models(p, my_models);
+  CascadePlan plan = cascade_plan(p->uid, s->uid, rng, my_models, model_bins, pm.data(), s->order.data(), s->len.data(), s->maxL, s->nbins, opt, ctx->plan_key, ctx->plan_groups);
+  if (plan.verdict == PLAN_NO_PAIRS) { st.ms_total = now_ms() - t_start; return 0; }
+  if (plan.verdict != PLAN_GO) return 2;          // over the pair budget or too many groups: host-driven cascade, turn still to be taken
   hipStream_t ms = ctx->stream;
-  // Parts by sequence length: the long sequences of every bin (a prefix of its length-sorted order) are scanned first, so that their
-  // chains -- every stage lasts as long as its longest sequence -- run underneath the SSV launches of the parts behind them, and what
-  // is left after the last SSV launch is the chain of the shortest sequences only.
-  const uint32_t nbins = s->nbins;
-  // cut[k][b] .. cut[k+1][b] = part k of bin b's length-sorted order (lengths descend along it); CKM_LONG_SHARE="0.25,0.5" gives the
-  // shares of the residues of all parts but the last.  Two parts by default (the longest sequences holding a quarter of the residues,
-  // then the rest); a third part of the shortest sequences, scanned last so that only short chains are left at the end, was measured
-  // and does not pay: 18 more launches and chains cost what the shorter tail gains (cfg2: 86.4-88.0 ms against 85.3).
-  std::vector<std::vector<uint32_t>> cut(1, rng.lo);
-  int nparts = 1, Lcut = 0;
-  std::vector<int> Lcuts;
-  {
-    uint64_t split_min = 2000000;
-    if (const char *e = getenv("CKM_SPLIT_MIN_PAIRS")) split_min = strtoull(e, nullptr, 10);
-    std::vector<double> shares{0.25};
-    if (const char *e = getenv("CKM_LONG_SHARE")) {
-      shares.clear();
-      for (const char *q = e; *q;) {
-        char *end = nullptr;
-        const double v = strtod(q, &end);
-        if (end == q) break;
-        if (v > 0.0 && v < 1.0) shares.push_back(v);
-        if (*end != ',') break;
-        q = end + 1;
-      }
-    }
-    if (total_pairs >= split_min && !shares.empty()) {
-      std::vector<uint64_t> by_len((size_t)s->maxL + 2, 0);
-      uint64_t total = 0;
-      for (uint32_t b = 0; b < nbins; ++b) for (uint32_t k = rng.lo[b]; k < rng.hi[b]; ++k) { const int L = s->len[s->order[k]]; by_len[L] += (uint64_t)L; total += (uint64_t)L; }
-      uint64_t acc = 0; double want = 0.0; size_t si = 0;
-      want = shares[0];
-      for (int L = s->maxL; L >= 1 && si < shares.size(); --L) {
-        acc += by_len[L];
-        if ((double)acc >= want * (double)total) {
-          if (L - 1 > 0 && (Lcuts.empty() || L - 1 < Lcuts.back())) Lcuts.push_back(L - 1);      // part boundary: lengths > L-1 | <= L-1
-          if (++si < shares.size()) want += shares[si];
-        }
-      }
-      for (int lc : Lcuts) {
-        std::vector<uint32_t> c(nbins);
-        for (uint32_t b = 0; b < nbins; ++b) {
-          uint32_t lo = rng.lo[b], hi = rng.hi[b];                 // first position with len <= lc
-          while (lo < hi) { const uint32_t m = (lo + hi) / 2; if (s->len[s->order[m]] > lc) lo = m + 1; else hi = m; }
-          c[b] = lo;
-        }
-        cut.push_back(std::move(c));
-      }
-      nparts = (int)Lcuts.size() + 1;
-      if (!Lcuts.empty()) Lcut = Lcuts[0];
-    }
+  if (plan.resident) { st.pairs_ssv += ctx->plan_pairs; st.residue_hmm += ctx->plan_residue_hmm; st.cells_ssv += ctx->plan_cells; }
+  else {
+    const BlockTable bt = std::move(plan.table);          // (the blocks are not needed once they are on the device)
+    st.pairs_ssv += bt.pairs; st.residue_hmm += bt.residues; st.cells_ssv += bt.cells;
+    ctx->work.ensure(bt.work.size() * sizeof(SsvBlockWork));
+    // (staged, copied by a kernel on a high-priority stream: see Stager)
+    ctx->stager.begin(bt.work.size() * sizeof(SsvBlockWork));
+    ctx->stager.put(ctx->late[2], ctx->work.p, bt.work.data(), bt.work.size() * sizeof(SsvBlockWork));
+    HIPCHK(hipStreamSynchronize(ctx->late[2]));  // the host waits, so everything queued below comes after
+    ctx->plan_key = plan.key; ctx->plan_groups = plan.groups; ctx->plan_nblocks = bt.work.size(); ctx->plan_pairs = bt.pairs; ctx->plan_residue_hmm = bt.residues; ctx->plan_cells = bt.cells;
   }
-  cut.push_back(rng.hi);
-  // key = part * 1000 + code of the SSV launch class, the code growing with the length of the models (groups are launched heaviest first):
-  // 8-lane classes 100 + Q8 (models of <= 512 nodes) -> Q8, 16-lane classes Q -> 40 + Q, kSsvNone -> 105
-  auto enc = [](int cls) { return cls >= 100 ? cls - 100 : 40 + cls; };
-  auto dec = [](int code) { return code < 40 ? 100 + code : code - 40; };
-  std::vector<std::pair<int, std::pair<size_t, size_t>>> groups;
-  {
-    std::vector<uint64_t> key{p->uid, s->uid, pair_budget, (uint64_t)Lcut, rng.tag, 0xdeull};
-    for (int lc : Lcuts) key.push_back(0xc0000000ull + (uint64_t)lc);
-    for (auto &mw : mws) { key.push_back(0xffffffffull + mw.model); for (uint32_t b : model_bins[mw.model]) key.push_back(b); }
-    if (key == ctx->plan_key) {
-      groups = ctx->plan_groups;
-      st.pairs_ssv += ctx->plan_pairs; st.residue_hmm += ctx->plan_residue_hmm; st.cells_ssv += ctx->plan_cells;
-    } else {
-      // runs = the sequences of one (model, bin, part), already longest first; a launch takes the first block of every run, then the
-      // second of every run, ...: its blocks come out (nearly) longest first without sorting a million of them (a block's time is set
-      // by its first = longest sequence, and the few very long ones must not start last)
-      struct Run { uint32_t model, first, count; uint64_t pair0; };
-      std::map<int, std::vector<Run>> runs;
-      uint64_t c_pairs = 0, c_res = 0, c_cells = 0;
-      for (auto &mw : mws) {
-        const int Q = ssv_class(p->prof[mw.model]);
-        uint64_t pb = mw.pair_base;
-        for (uint32_t b : model_bins[mw.model]) {
-          const uint32_t o0 = rng.lo[b], n = rng.hi[b] - o0;
-          for (int part = 0; part < nparts; ++part) {
-            const uint32_t a0 = cut[part][b] - o0, a1 = cut[part + 1][b] - o0;
-            if (a1 > a0) runs[part * 1000 + enc(Q)].push_back({mw.model, o0 + a0, a1 - a0, pb + a0});
-          }
-          pb += n; c_res += rng.res[b]; c_cells += rng.res[b] * (uint64_t)p->prof[mw.model].M;
-        }
-        c_pairs += mw.npairs;
-      }
-      st.pairs_ssv += c_pairs; st.residue_hmm += c_res; st.cells_ssv += c_cells;
-      std::vector<SsvBlockWork> allw;
-      for (auto &kv : runs) {
-        const int Q = dec(kv.first % 1000); const uint32_t per_block = ssv_per_block(Q);
-        const size_t first = allw.size();
-        std::vector<Run> &rv = kv.second;
-        std::stable_sort(rv.begin(), rv.end(), [&](const Run &x, const Run &y) { return s->len[s->order[x.first]] > s->len[s->order[y.first]]; });
-        for (uint32_t a = 0;; a += per_block) {
-          bool any = false;
-          for (const Run &r : rv) if (a < r.count) {
-            any = true;
-            SsvBlockWork w; w.model = r.model; w.list_start = r.first + a; w.count = std::min(per_block, r.count - a); w.pair_start = (uint32_t)(r.pair0 + a);
-            allw.push_back(w);
-          }
-          if (!any) break;
-        }
-        groups.push_back({kv.first, {first, allw.size() - first}});
-      }
-      ctx->work.ensure(allw.size() * sizeof(SsvBlockWork));
-      // (staged, copied by a kernel on a high-priority stream: see Stager)
-      ctx->stager.begin(allw.size() * sizeof(SsvBlockWork));
-      ctx->stager.put(ctx->late[2], ctx->work.p, allw.data(), allw.size() * sizeof(SsvBlockWork));
-      HIPCHK(hipStreamSynchronize(ctx->late[2]));  // the host waits, so everything queued below comes after
-      ctx->plan_key = key; ctx->plan_groups = groups; ctx->plan_nblocks = allw.size(); ctx->plan_pairs = c_pairs; ctx->plan_residue_hmm = c_res; ctx->plan_cells = c_cells;
-    }
-  }
-  // per group: its pairs and the Viterbi / Forward register classes of its models
-  struct Sub { int Q; int maxM = 0; size_t first, nblocks; uint64_t pairs = 0; bool vit[NVC] = {false}, fb[NFC] = {false};
-               uint32_t cap_cand = 0, cap_nores = 0, cap_f = 0, cap_e = 0, cap_r = 0; size_t o_cand = 0, o_nores = 0, o_vq = 0, o_f = 0, o_e = 0, o_r = 0; };
-  std::vector<Sub> subs;
-  {
-    std::map<int, size_t> at;
-    for (auto &g : groups) { Sub sb; sb.Q = dec(g.first % 1000); sb.first = g.second.first; sb.nblocks = g.second.second; at[g.first] = subs.size(); subs.push_back(sb); }
-    for (auto &mw : mws) {
-      for (int part = 0; part < nparts; ++part) {
-        uint64_t np = 0;                                      // the model's pairs in this part
-        for (uint32_t b : model_bins[mw.model]) np += cut[part + 1][b] - cut[part][b];
-        auto it = at.find(part * 1000 + enc(ssv_class(p->prof[mw.model])));
-        if (it == at.end()) continue;                         // (no sequence of this part in the model's bins)
-        Sub &sb = subs[it->second]; sb.pairs += np; sb.vit[p->dm[mw.model].vit_cls] = true; sb.vit[p->dm[mw.model].vitx_cls] = true; sb.fb[p->dm[mw.model].fb_cls] = true; sb.maxM = std::max(sb.maxM, p->prof[mw.model].M);
-      }
-    }
-  }
+  const PlanGroups &groups = plan.groups;
+  const std::vector<Sub> &subs = plan.subs;
+  const int Lcut = plan.parts.Lcut;
+  const uint64_t total_pairs = plan.total_pairs;
   const size_t NG = subs.size();
-  if (NG > 192) return 2;                          // (grp_ev; 2 parts x (30 eight-lane + 29 sixteen-lane SSV classes + 1) at most)
   CKM_TRACE_PT("plan ready");
 
   // ---- capacities: shares of the pairs (the divisors halve when a table overflowed on an earlier call), tables ----
-  Worker::CascadeCaps &cp = ctx->caps;
-  size_t tot_cand = 0, tot_nores = 0, tot_f = 0, tot_e = 0, tot_r = 0;
-  // (tests: CKM_CAP_SHRINK=n makes every table n times smaller than its share and drops the floors, to force the overflow -> host-driven path)
-  const uint64_t shrink = getenv("CKM_CAP_SHRINK") ? std::max(1, atoi(getenv("CKM_CAP_SHRINK"))) : 1;
-  auto capof = [&](uint64_t pairs, uint32_t div, uint64_t floor_) {
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(shrink > 1 ? 8 : floor_, pairs / ((uint64_t)div * shrink)), 0x7ffffff0ull); };
-  for (Sub &sb : subs) {
-    sb.cap_cand = capof(sb.pairs, cp.div_cand, cp.fl_cand);
-    sb.cap_nores = sb.Q == kSsvNone ? (uint32_t)std::min<uint64_t>(sb.pairs + 64, 0x7ffffff0ull)     // no SSV for these models: every pair is recomputed exactly
-                                    : capof(sb.pairs, cp.div_nores, cp.fl_nores);
-    sb.cap_f = capof(sb.pairs, cp.div_fwork, cp.fl_fwork);
-    sb.cap_e = capof(sb.pairs, cp.div_ework, cp.fl_ework);
-    sb.cap_r = capof(sb.pairs, cp.div_rwork, cp.fl_rwork);
-    sb.o_cand = tot_cand; tot_cand += sb.cap_cand; sb.o_nores = tot_nores; tot_nores += sb.cap_nores;
-    sb.o_vq = sb.o_cand * NVC;
-    sb.o_f = tot_f * NFC; tot_f += sb.cap_f; sb.o_e = tot_e * NFC; tot_e += sb.cap_e; sb.o_r = tot_r * NFC; tot_r += sb.cap_r;
-  }
-  auto grow = [](uint32_t &v, uint64_t want) { if (v < want) v = (uint32_t)std::min<uint64_t>(want, 0xfffffff0ull); };
-  grow(cp.fwork, tot_f); grow(cp.ework, tot_e); grow(cp.rwork, tot_r);
-  grow(cp.pass, std::max<uint64_t>(1 << 13, tot_e)); grow(cp.reg, (uint64_t)cp.ework + cp.rwork);
-  grow(cp.events_f, std::max<uint64_t>(1 << 18, (uint64_t)cp.fwork * 16));
-  grow(cp.events_e, std::max<uint64_t>(1 << 16, (uint64_t)cp.ework * 16));
-  // (the export buffer of the ensembles is sized for the regions SEEN so far, with room -- not for the region tables' capacity, which is
-  //  a floor per group times the groups; an overflow doubles it: CS_RWORK)
-  cp.hens = std::max<uint64_t>(cp.hens, std::min<uint64_t>(cp.rwork, (uint64_t)4 * cp.seen_rwork + 8192) * (256 + ENS_NSAMPLES * 16 * 4 + 1024));
-  // the float workspace: an estimate from the pairs (special rows of ~0.3 % of them, matrices of ~0.06 %), within the lane's budget
-  // the float workspace, estimated from the cells the search is expected to fill: a marker model finds about one domain in a bin it is
-  // scanned against, and a domain costs its envelope's matrix (about M rows of Mp floats, three arrays in place) -- so the demand follows
-  // sum over models of (bins scanned against the model) x (Mp + 64) x Mp, whatever the number of ORFs in those bins and whichever kind
-  // of search it is (43 phylogenetic markers against hundreds of bins, or a lineage's hundreds of models against a few bins).  Rounds
-  // 2-4 priced it per (pair x model position), which follows the ORF count instead: one factor could not fit both kinds (round 3: 156 GB
-  // allocated for 76 GB used), two factors still overshot 2x.  Measured on the 1000-bin workload (profiles/r04r_workspace_per_cell.txt):
-  // 9.78-9.82 B per cell where every model is present in every bin (the 43 phylogenetic markers), 4.1-4.7 where about half of a
-  // lineage's models are; the first estimate is 11 B (the first kind + 12 %).  A search that outgrows the estimate falls back once
-  // (deferred regions) and leaves its measured bytes per cell (+15 %) for the next calls.
-  double cell_sum = 0.0;
-  {
-    for (auto &mw : mws) { const double Mp = (double)(p->prof[mw.model].fbQ * NL); cell_sum += (double)model_bins[mw.model].size() * (Mp + 64.0) * Mp; }
-    const uint64_t est = (uint64_t)(cell_sum * cp.ws_per_cell + (double)total_pairs * 24.0) + ((uint64_t)256 << 20);
-    const size_t want = (size_t)std::min<uint64_t>(std::max<uint64_t>(est, (uint64_t)1 << 30), (uint64_t)ctx->ws_budget);
-    if (ctx->ws.cap < want) ctx->ws.ensure(want);
-  }
+  CascadeCaps &cp = ctx->caps;
+  const TableSizes ts = size_tables(plan.subs, cp, plan.mws, pm.data(), model_bins, total_pairs, opt.shrink, ctx->ws_budget);
+  if (ctx->ws.cap < ts.ws_want) ctx->ws.ensure(ts.ws_want);
   const uint64_t ws_floats = ctx->ws.cap / 4;
   CKM_TRACE_PT("workspace ready");
   uint32_t *d_gcnt = dev_table<uint32_t>(ctx->c_cnt, (NG + 1) * CC_SIZE);        // block 0: counters shared by the groups; block 1 + g: group g's
   unsigned long long *d_tops = dev_table<unsigned long long>(ctx->c_tops, 4);
   CascadeDev cd0; memset(&cd0, 0, sizeof(cd0));
-  PairRec *d_cand = dev_table<PairRec>(ctx->c_cand, tot_cand), *d_nores = dev_table<PairRec>(ctx->c_nores, tot_nores);
-  float *d_bias = dev_table<float>(ctx->c_bias, tot_cand * 2), *d_vfast = dev_table<float>(ctx->c_vfast, tot_cand), *d_vexact = dev_table<float>(ctx->c_vexact, tot_cand);
-  uint32_t *d_vflag = dev_table<uint32_t>(ctx->c_vflag, tot_cand); uint8_t *d_route = dev_table<uint8_t>(ctx->c_route, tot_cand);
-  uint32_t *d_vq = dev_table<uint32_t>(ctx->c_vq, tot_cand * NVC), *d_vxq = dev_table<uint32_t>(ctx->c_vxq, tot_cand * NVC);
-  uint32_t *d_fq = dev_table<uint32_t>(ctx->c_fq, tot_f * NFC), *d_bq = dev_table<uint32_t>(ctx->c_bq, tot_f * NFC);
-  uint32_t *d_eq = dev_table<uint32_t>(ctx->c_eq, tot_e * NFC), *d_rq = dev_table<uint32_t>(ctx->c_rq, tot_r * NFC);
+  PairRec *d_cand = dev_table<PairRec>(ctx->c_cand, ts.tot_cand), *d_nores = dev_table<PairRec>(ctx->c_nores, ts.tot_nores);
+  float *d_bias = dev_table<float>(ctx->c_bias, ts.tot_cand * 2), *d_vfast = dev_table<float>(ctx->c_vfast, ts.tot_cand), *d_vexact = dev_table<float>(ctx->c_vexact, ts.tot_cand);
+  uint32_t *d_vflag = dev_table<uint32_t>(ctx->c_vflag, ts.tot_cand); uint8_t *d_route = dev_table<uint8_t>(ctx->c_route, ts.tot_cand);
+  uint32_t *d_vq = dev_table<uint32_t>(ctx->c_vq, ts.tot_cand * NVC), *d_vxq = dev_table<uint32_t>(ctx->c_vxq, ts.tot_cand * NVC);
+  uint32_t *d_fq = dev_table<uint32_t>(ctx->c_fq, ts.tot_f * NFC), *d_bq = dev_table<uint32_t>(ctx->c_bq, ts.tot_f * NFC);
+  uint32_t *d_eq = dev_table<uint32_t>(ctx->c_eq, ts.tot_e * NFC), *d_rq = dev_table<uint32_t>(ctx->c_rq, ts.tot_r * NFC);
   cd0.gcnt = d_gcnt;
   cd0.fwork = dev_table<FbWork>(ctx->c_fwork, cp.fwork); cd0.cap_fwork = cp.fwork;
   cd0.ework = dev_table<FbWork>(ctx->c_ework, cp.ework); cd0.cap_ework = cp.ework;
   cd0.rwork = dev_table<FbWork>(ctx->c_rwork, cp.rwork); cd0.ens = dev_table<EnsWork>(ctx->c_ens, cp.rwork); cd0.cap_rwork = cp.rwork;
   uint32_t *d_ensq = dev_table<uint32_t>(ctx->c_ensq, (size_t)4 * cp.rwork);       // region ids by sequence part
-  // zone 1: special rows and decoding terms of the parser items (~a few KB for ~0.3 % of the pairs: 64 B per pair until a search asked
-  // for more); zone 2: everything else
   {
-    const uint64_t z1 = std::min<uint64_t>(ws_floats / 2, ((uint64_t)((double)total_pairs * cp.z1_per_pair) + ((uint64_t)64 << 20)) / 4) & ~(uint64_t)31;
+    const uint64_t z1 = zone1_floats(ws_floats, total_pairs, cp);
     cd0.ws_top = d_tops; cd0.ws_cap = z1;
     cd0.ws2_top = d_tops + 2; cd0.ws2_base = z1; cd0.ws2_cap = ws_floats - z1;
   }
@@ -789,16 +605,7 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   HIPCHK(hipEventRecord(ctx->cev[0], ms));
   for (int k = 0; k < NS; ++k) HIPCHK(hipStreamWaitEvent(ctx->side[k], ctx->cev[0], 0));
   {
-    std::vector<size_t> launch_order;                            // long part first; inside a part the heaviest register class first
-    {
-      size_t g0 = 0;                                             // groups are sorted by key = part * 1000 + class
-      for (int part = 0; part < nparts; ++part) {
-        size_t g1 = g0;
-        while (g1 < NG && groups[g1].first / 1000 == part) ++g1;
-        for (size_t g = g1; g-- > g0;) launch_order.push_back(g);
-        g0 = g1;
-      }
-    }
+    const std::vector<size_t> &launch_order = plan.order;       // long part first; inside a part the heaviest register class first
     // The trace ensembles of the multi-domain regions: ONE set of launches per sequence PART, behind the chains of all of the part's
     // groups, on a stream of their own.  A region's 200 traces run one after the other (one generator stream per region, as
     // hmmsearch carries it), so a launch lasts as long as its longest region -- tens of milliseconds; per group and register class, on the
@@ -925,72 +732,21 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   // ---- did everything fit? ----
   const uint32_t n_fwork = h_cnt[CC_FWORK], n_ework = h_cnt[CC_EWORK], n_rwork = h_cnt[CC_RWORK],
                  n_pass = h_cnt[CC_PASS], n_reg = h_cnt[CC_REG], n_evf = h_cnt[CC_EVENTS], n_eve = h_cnt[CC_EVENTS_E], status = h_cnt[CC_STATUS];
-  bool fits = status == 0;
   const bool tr = getenv("CKM_TRACE") != nullptr;
-  auto over = [&](const char *what, int g, int k, uint64_t n, uint64_t cap) {
-    fits = false; if (tr) fprintf(stderr, "ckm-trace w%d table %s (group %d, class %d) wanted %llu of %llu\n", ctx->id, what, g, k, (unsigned long long)n, (unsigned long long)cap); };
-  auto need = [&](const char *what, uint32_t &cap, uint32_t n) { if (n > cap) { over(what, -1, -1, n, cap); cap = (uint32_t)std::min<uint64_t>((uint64_t)n + n / 4 + 1024, 0xfffffff0ull); } };
-  cp.seen_rwork = std::max(cp.seen_rwork, n_rwork);
-  need("fwork", cp.fwork, n_fwork); need("ework", cp.ework, n_ework); need("rwork", cp.rwork, n_rwork); need("pass", cp.pass, n_pass);
-  need("reg", cp.reg, n_reg); need("events_f", cp.events_f, n_evf); need("events_e", cp.events_e, n_eve);
-  // A per-group table that overflowed is sized from what the group ASKED for (round 6): its divisor follows the observed share of the
-  // pairs and its floor the observed count (+25 %), so that the same kind of search fits the next time.  Rounds 2-5 halved the divisor
-  // once per search -- which changes nothing where the floor is the larger term: on inputs with many multi-domain regions (paralog
-  // families, low-complexity proteins: bench.py's hard_workload) the 256-entry region queues overflowed in EVERY search, and every search
-  // paid the host-driven cascade (profiles/r06q_hard_workload_overflows.txt).
-  // (the divisor still halves at most once per search, and only where it was the larger term: a small group's share says nothing about
-  //  the large ones -- regions follow the domains present, not the pairs scanned)
-  uint32_t halved = 0;
-  auto learn = [&](int kind, uint32_t &div, uint32_t &floor_, uint64_t pairs, uint64_t want) {
-    const uint64_t w = want + want / 4 + 16;
-    if ((pairs / std::max<uint64_t>(1, (uint64_t)div * shrink) >= floor_ || shrink > 1) && !((halved >> kind) & 1u)) { div = std::max<uint32_t>(1, div / 2); halved |= 1u << kind; }
-    if (shrink == 1) floor_ = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(floor_, w), 1u << 14);
-    // More than the floor may become (every group pays the floor, so it stays small): then the group's SHARE has to give it the entries,
-    // whatever the larger term was -- else max(pairs / div, floor) stays below `want` and this kind of search overflows in every call.  A
-    // group that asks for more entries than it has pairs (several envelopes or regions per pair) gets them from the floor after all.
-    if (shrink == 1 && w > (1u << 14)) {
-      const uint64_t d = pairs / w;
-      if (d >= 1) div = (uint32_t)std::min<uint64_t>(div, d);
-      else { div = 1; floor_ = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(floor_, w), 1u << 20); }
-    }
-  };
-  uint64_t n_cand = 0, n_nores = 0;
-  for (size_t g = 0; g < NG; ++g) {
-    const uint32_t *c = h_cnt + (1 + g) * CC_SIZE; const Sub &sb = subs[g];
-    n_cand += c[CC_CAND]; n_nores += c[CC_NORES];
-    if (c[CC_CAND] > sb.cap_cand) { over("cand", (int)g, -1, c[CC_CAND], sb.cap_cand); learn(0, cp.div_cand, cp.fl_cand, sb.pairs, c[CC_CAND]); }
-    if (c[CC_NORES] > sb.cap_nores) { over("nores", (int)g, -1, c[CC_NORES], sb.cap_nores); if (sb.Q != kSsvNone) learn(1, cp.div_nores, cp.fl_nores, sb.pairs, c[CC_NORES]); }
-    for (int k = 0; k < NVC; ++k) {
-      st.pairs_vit += c[CC_VQ + k]; st.pairs_vit_exact += c[CC_VXQ + k];
-      const uint32_t v = std::max(c[CC_VQ + k], c[CC_VXQ + k]);
-      if (v > sb.cap_cand) { over("vq", (int)g, k, v, sb.cap_cand); learn(0, cp.div_cand, cp.fl_cand, sb.pairs, v); }
-    }
-    for (int k = 0; k < NFC; ++k) {
-      const uint32_t f = std::max(c[CC_FQ + k], c[CC_BQ + k]);
-      if (f > sb.cap_f) { over("fq", (int)g, k, f, sb.cap_f); learn(2, cp.div_fwork, cp.fl_fwork, sb.pairs, f); }
-      if (c[CC_EQ + k] > sb.cap_e) { over("eq", (int)g, k, c[CC_EQ + k], sb.cap_e); learn(3, cp.div_ework, cp.fl_ework, sb.pairs, c[CC_EQ + k]); }
-      if (c[CC_RQ + k] > sb.cap_r) { over("rq", (int)g, k, c[CC_RQ + k], sb.cap_r); learn(4, cp.div_rwork, cp.fl_rwork, sb.pairs, c[CC_RQ + k]); }
-    }
-  }
-  if (status & CS_RWORK) cp.hens *= 2;
-  // zone 2 ran out (regions were deferred to the host): size the workspace from what this search asked for, for the next calls
+  // what the tables, divisors, floors and workspace rates learn from this search (cascade_plan.h); the lane's capacities grow here
+  const Lesson lesson = learn_from(h_cnt, h_tops, subs, cp, opt.shrink, total_pairs, ts.cell_sum, cd0.ws_cap, cd0.ws2_cap);
+  if (tr) for (const Overflow &o : lesson.over)
+    fprintf(stderr, "ckm-trace w%d table %s (group %d, class %d) wanted %llu of %llu\n", ctx->id, o.what, o.group, o.cls, (unsigned long long)o.wanted, (unsigned long long)o.cap);
+  st.pairs_vit += lesson.pairs_vit; st.pairs_vit_exact += lesson.pairs_vit_exact;
+  const uint64_t n_cand = lesson.n_cand, n_nores = lesson.n_nores;
   st.ws_cap_bytes = ctx->ws.cap; st.ws_used_bytes = (std::min<uint64_t>(h_tops[0], cd0.ws_cap) + h_tops[2]) * 4;
-  // the bump allocator counts every request, granted or not: after an overflow the search's whole demand is known, and the next one of its
-  // kind gets that (+15 %) instead of a blind x1.5
-  // (zone 1 the same way, per pair: where most pairs are hits -- a small database of families that every protein carries -- 64 B per
-  //  pair is a third of the demand, and without this such a search took the host-driven cascade in every call)
-  // (never shrinks; z1 is also held to half of the workspace: where THAT is the smaller term the search asks for more than the workspace
-  //  budget gives and stays host-driven -- the trace says so)
   if (h_tops[0] > cd0.ws_cap && tr && cd0.ws_cap == ((ws_floats / 2) & ~(uint64_t)31))
     fprintf(stderr, "ckm-trace w%d workspace zone 1 is held to half of the workspace (%.3f GB) and this search asked for %.3f GB: it stays on the host-driven cascade\n", ctx->id,
             (double)cd0.ws_cap * 4 / 1e9, (double)h_tops[0] * 4 / 1e9);
-  if (h_tops[0] > cd0.ws_cap) cp.z1_per_pair = std::max(cp.z1_per_pair, (float)(1.15 * (double)h_tops[0] * 4.0 / (double)std::max<uint64_t>(total_pairs, 1)));
-  if (h_tops[2] > cd0.ws2_cap)
-    cp.ws_per_cell = std::max(cp.ws_per_cell, (float)(1.15 * (double)(h_tops[2] + cd0.ws_cap) * 4.0 / std::max(cell_sum, 1.0)));
   if (tr) fprintf(stderr, "ckm-trace w%d workspace: %.3f GB held, %.3f GB asked for by this search (zone 1 %.3f of %.3f, zone 2 %.3f of %.3f), %.3e cells -> %.2f B per cell (estimate %.2f)\n", ctx->id,
                   (double)ctx->ws.cap / 1e9, (double)(h_tops[0] + h_tops[2]) * 4 / 1e9, (double)h_tops[0] * 4 / 1e9, (double)cd0.ws_cap * 4 / 1e9, (double)h_tops[2] * 4 / 1e9,
-                  (double)cd0.ws2_cap * 4 / 1e9, cell_sum, (double)(h_tops[0] + h_tops[2]) * 4 / std::max(cell_sum, 1.0), (double)cp.ws_per_cell);
-  if (!fits) {
+                  (double)cd0.ws2_cap * 4 / 1e9, ts.cell_sum, (double)(h_tops[0] + h_tops[2]) * 4 / std::max(ts.cell_sum, 1.0), (double)cp.ws_per_cell);
+  if (!lesson.fits) {
     if (getenv("CKM_TRACE")) fprintf(stderr, "ckm-trace w%d device cascade did not fit (status 0x%x): host-driven cascade for this lane\n", ctx->id, status);
     return 1;
   }
