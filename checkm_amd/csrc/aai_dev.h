@@ -13,6 +13,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "ckm_internal.h"
 #include "wave_const.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -153,7 +154,9 @@ struct Group {
 // Whether the arguments of a call can be taken, and in `why` what is wrong with them: ARGS_INVALID is a bad argument, ARGS_RANGE a size
 // limit.  group_row_off[ngroups + 1] counts rows and row_off[group_row_off[ngroups] + 1] counts bytes of `text`; both start at 0 and never
 // fall.  No entry of row_off is read before group_row_off is known to be in order.
-enum { ARGS_OK = 0, ARGS_INVALID = 1, ARGS_RANGE = 2 };
+using ckm::ARGS_INVALID;
+using ckm::ARGS_OK;
+using ckm::ARGS_RANGE;
 inline int check_args(uint32_t ngroups, const uint64_t *group_row_off, const uint64_t *row_off, const char *text, std::string &why) {
   auto no = [&](int kind, const std::string &m) { why = m; return kind; };
   if (!group_row_off || !row_off) return no(ARGS_INVALID, "NULL argument");

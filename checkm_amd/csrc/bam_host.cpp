@@ -1,7 +1,6 @@
 // bam_host.cpp -- BGZF and BAM on the host (SAMv1 sections 4.1, 4.2): see bam_host.h.
 #include "bam_host.h"
 #include <zlib.h>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 
@@ -11,7 +10,6 @@ namespace {
 
 inline uint32_t ld16(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
 inline uint32_t ld32(const uint8_t *p) { return ld16(p) | ld16(p + 2) << 16; }
-inline double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
 struct Block { uint64_t comp_off, file_off; uint32_t comp_len, isize, crc; uint64_t out_off; };
 
@@ -50,7 +48,7 @@ void Reader::compact() {
 
 bool Reader::more(uint64_t want) {
   if (eof_) return false;
-  const auto t0 = std::chrono::steady_clock::now();
+  const WallClock t0;
   std::vector<Block> blocks;
   comp_.clear();
   uint64_t got = 0;
@@ -82,9 +80,9 @@ bool Reader::more(uint64_t want) {
     blocks.push_back({c0, file_off_, (uint32_t)(rest - 8), isize, ld32(tail), len_ + got});
     got += isize; file_off_ += (uint64_t)bsize + 1; ++nblocks_;
   }
-  timing.ms_read += ms_since(t0);
+  timing.ms_read += t0.ms();
   if (blocks.empty()) return false;
-  const auto t1 = std::chrono::steady_clock::now();
+  const WallClock t1;
   if (buf_.size() < len_ + got) buf_.resize(len_ + got + (got >> 3));
   auto work = [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
@@ -95,7 +93,7 @@ bool Reader::more(uint64_t want) {
   };
   if (pool_) pool_->run(blocks.size(), 16, work); else work(0, blocks.size());
   len_ += got; inflated_ += got;
-  timing.ms_inflate += ms_since(t1);
+  timing.ms_inflate += t1.ms();
   return true;
 }
 
@@ -141,7 +139,7 @@ bool Reader::next(uint64_t budget, Batch &b) {
   if (len_ - cur_ < budget && !eof_) { compact(); more(budget - len_ + (1 << 16)); }      // (slack: the record that straddles the budget)
   const int64_t n_ref = (int64_t)names_.size();
   for (;;) {
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     const uint8_t *d = buf_.data() + cur_;
     const uint64_t n = len_ - cur_;
     uint64_t p = 0;
@@ -165,7 +163,7 @@ bool Reader::next(uint64_t budget, Batch &b) {
       b.offsets.push_back((uint32_t)p);
       p += 4 + (uint64_t)bs;
     }
-    timing.ms_offsets += ms_since(t0);
+    timing.ms_offsets += t0.ms();
     if (!b.offsets.empty() && (p >= budget || eof_)) {
       if (eof_ && p < budget && p != n) {
         // the file ended inside a record

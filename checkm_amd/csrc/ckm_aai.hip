@@ -1,7 +1,6 @@
 // ckm_aai.hip -- C ABI of the all-pairs amino-acid identity of AminoAcidIdentity.run (kernels_aai.hip): the rows of every group in; per
 // pair, in the reference's order, the mismatches, the compared columns and the identity out.  The group table and pair_off go up once;
 // the packed text and the outputs travel in batches of a byte budget, so the memory of a call on the device does not grow with n^2.
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -29,24 +28,22 @@ extern "C" int ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group
     if (!ctx || !out) throw Error(CKM_EINVAL, "NULL argument");
     *out = nullptr;
     std::string why;
-    const int kind = aai::check_args(ngroups, group_row_off, row_off, text, why);
-    if (kind != aai::ARGS_OK) throw Error(kind == aai::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL, why);
+    refuse(aai::check_args(ngroups, group_row_off, row_off, text, why), why);
     budget_bytes = batch_budget(budget_bytes, "CKM_AAI_BATCH_MB", 64);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     std::unique_ptr<ckm_aai> o(new ckm_aai());
     aai::Packed P;
     aai::pack(ngroups, group_row_off, row_off, text, P);
-    o->ms_pack = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ms_pack = t0.ms();
     o->ngroups = ngroups; o->npairs = P.pair_off[ngroups];
     o->mismatches.resize(o->npairs); o->compared.resize(o->npairs); o->identity.resize(o->npairs);
     if (o->npairs) {
       cs.open(ctx->device);
       DevBuf d_groups, d_off, d_text, d_out;
       PinnedBuf h_out;
-      d_groups.ensure((size_t)ngroups * sizeof(aai::Group)); d_off.ensure(((size_t)ngroups + 1) * 8);
       cs.timed(o->ms_upload, [&] {
-        HIPCHK(hipMemcpyAsync(d_groups.p, P.groups.data(), (size_t)ngroups * sizeof(aai::Group), hipMemcpyHostToDevice, cs.st));
-        HIPCHK(hipMemcpyAsync(d_off.p, P.pair_off.data(), ((size_t)ngroups + 1) * 8, hipMemcpyHostToDevice, cs.st));
+        cs.put(d_groups, P.groups.data(), (size_t)ngroups * sizeof(aai::Group));
+        cs.put(d_off, P.pair_off.data(), ((size_t)ngroups + 1) * 8);
       });
       aai::Batch B;
       uint64_t cursor = 0;
@@ -60,11 +57,11 @@ extern "C" int ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group
           if (P.groups[g].n > 1 && (P.groups[g].text_off < B.text_lo || P.groups[g].text_off + aai::group_bytes(P.groups[g]) > B.text_lo + B.text_bytes))
             throw Error(CKM_EINVAL, "internal: a group leaves its batch");
         // the outputs of a batch in one buffer: identity (8-byte values) first, then the two counts
-        d_text.ensure(B.text_bytes); d_out.ensure((size_t)np * aai::PAIR_BYTES); h_out.ensure((size_t)np * aai::PAIR_BYTES);
+        d_out.ensure((size_t)np * aai::PAIR_BYTES); h_out.ensure((size_t)np * aai::PAIR_BYTES);
         double *da = d_out.as<double>();
         int32_t *dm = reinterpret_cast<int32_t *>(da + np), *dc = dm + np;
         cs.mark(0);
-        if (B.text_bytes) HIPCHK(hipMemcpyAsync(d_text.p, P.text.data() + B.text_lo, B.text_bytes, hipMemcpyHostToDevice, cs.st));
+        cs.put(d_text, P.text.data() + B.text_lo, B.text_bytes);
         cs.mark(1);
         launch_aai_pairs(cs.st, d_text.as<uint8_t>(), B.text_lo, d_groups.as<aai::Group>(), d_off.as<uint64_t>(), B.g_lo, B.g_hi, B.p0, np, dm, dc, da);
         HIPCHK(hipGetLastError());
@@ -84,7 +81,7 @@ extern "C" int ckm_aai_run(ckm_ctx *ctx, uint32_t ngroups, const uint64_t *group
       }
     }
     o->pair_off.swap(P.pair_off);
-    o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ms_total = t0.ms();
     *out = o.release();
   });
 }

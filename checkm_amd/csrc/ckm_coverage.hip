@@ -3,7 +3,6 @@
 // per-reference counters; every phase is waited for (the reader's buffer is reused by the next batch), so inflating and the kernel do
 // not overlap.  The counters come down once, at the end.  CoverageWindows (`checkm gc_bias_plot`; kernels_covwin.hip) runs the same batch
 // loop with its own chain and two more accumulators, the window arrays, which a scan turns into window sums after the last batch.
-#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -94,24 +93,22 @@ int coverage_pass(ckm_ctx *ctx, ckm_bam *b, uint64_t budget_bytes, Timing *timin
   return guarded([&] {
     check();
     memset(timing, 0, sizeof *timing);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     bam::Reader &rd = *b->reader;
     const uint64_t budget = bam::batch_budget(budget_bytes);
     ck.open(ctx->device);
     DevBuf d_data, d_off, d_err;
-    d_err.ensure(8);
     uint64_t slot = cv::NO_ERROR;
     ck.timed(timing->ms_upload, [&] {
       begin(ck);
-      HIPCHK(hipMemcpyAsync(d_err.p, &slot, 8, hipMemcpyHostToDevice, ck.st));
+      ck.put(d_err, &slot, 8);
     });
     bam::Batch bt;
     while (rd.next(budget, bt)) {
       const size_t nrec = bt.offsets.size();
-      d_data.ensure(bt.bytes); d_off.ensure(nrec * 4);
       ck.timed(timing->ms_upload, [&] {
-        HIPCHK(hipMemcpyAsync(d_data.p, bt.data, bt.bytes, hipMemcpyHostToDevice, ck.st));
-        HIPCHK(hipMemcpyAsync(d_off.p, bt.offsets.data(), nrec * 4, hipMemcpyHostToDevice, ck.st));
+        ck.put(d_data, bt.data, bt.bytes);
+        ck.put(d_off, bt.offsets.data(), nrec * 4);
       });
       ck.timed(timing->ms_kernel, [&] {
         launch(ck.st, d_data.as<uint8_t>(), d_off.as<uint32_t>(), (uint32_t)nrec, bt.first_ordinal, d_err.as<unsigned long long>());
@@ -132,7 +129,7 @@ int coverage_pass(ckm_ctx *ctx, ckm_bam *b, uint64_t budget_bytes, Timing *timin
     end(ck);
     timing->blocks = rd.blocks(); timing->inflated_bytes = rd.inflated();
     timing->ms_read = rd.timing.ms_read; timing->ms_inflate = rd.timing.ms_inflate; timing->ms_offsets = rd.timing.ms_offsets;
-    timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timing->ms_total = t0.ms();
   });
 }
 

@@ -3,7 +3,6 @@
 // matrices and join state fit the byte budget.  A batch is gathered, counted, turned into distances and joined by launches on the call's
 // stream -- the join loop is queued whole, the host waits once per batch -- and only its merge rows come back, at the batch's first tree
 // in the caller's arrays, so no result depends on the budget.
-#include <chrono>
 #include <string>
 #include <vector>
 #include "ckm_host.h"
@@ -26,10 +25,9 @@ extern "C" int ckm_gtree_run(ckm_ctx *ctx, const ckm_gtree_args *a, uint64_t bud
   return guarded([&] {
     if (!ctx || !a || !out) throw Error(CKM_EINVAL, "NULL argument");
     std::string why;
-    const int kind = gtree_check_args(a, why);
-    if (kind != gtree::ARGS_OK) throw Error(kind == gtree::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL, why);
+    refuse(gtree_check_args(a, why), why);
     if ((out->compared && !out->differ) || (out->merge_ij && !out->merge_len)) throw Error(CKM_EINVAL, "NULL argument");
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     budget_bytes = batch_budget(budget_bytes, "CKM_GTREE_BATCH_MB", 2048);
     const bool from_matrix = a->matrix != nullptr;
     const uint32_t N = a->nrows, L = from_matrix ? 0 : a->ncols, T = gtree::trees_of(gtree_args_of(a));
@@ -40,8 +38,8 @@ extern "C" int ckm_gtree_run(ckm_ctx *ctx, const ckm_gtree_args *a, uint64_t bud
     DevBuf d_text, d_enc, d_cols, d_rep, d_cmp, d_dif, d_D, d_R, d_la, d_lb, d_rq, d_rb, d_ij, d_len;
     if (!from_matrix) {
       cs.timed(I.ms_upload, [&] {
-        d_text.ensure(a->ntext_bytes); d_enc.ensure(enc_bytes);
-        HIPCHK(hipMemcpyAsync(d_text.p, a->text, a->ntext_bytes, hipMemcpyHostToDevice, cs.st));
+        d_enc.ensure(enc_bytes);
+        cs.put(d_text, a->text, a->ntext_bytes);
         launch_gt_encode(cs.st, d_text.as<uint8_t>(), N, L, d_enc.as<uint8_t>());
         HIPCHK(hipGetLastError());
       });
@@ -73,8 +71,8 @@ extern "C" int ckm_gtree_run(ckm_ctx *ctx, const ckm_gtree_args *a, uint64_t bud
           const uint32_t nb = (a->base && t0t == 0) ? 1u : 0u, nr = nt - nb, r0 = t0t + nb - a->base;
           d_cmp.ensure(NN * 4 * nt); d_dif.ensure(NN * 4 * nt);
           if (nr) {
-            d_cols.ensure((uint64_t)nr * L * 4); d_rep.ensure(enc_bytes * nr);
-            cs.timed(I.ms_upload, [&] { HIPCHK(hipMemcpyAsync(d_cols.p, a->cols + (uint64_t)r0 * L, (uint64_t)nr * L * 4, hipMemcpyHostToDevice, cs.st)); });
+            d_rep.ensure(enc_bytes * nr);
+            cs.timed(I.ms_upload, [&] { cs.put(d_cols, a->cols + (uint64_t)r0 * L, (uint64_t)nr * L * 4); });
             cs.timed(I.ms_gather, [&] { launch_gt_gather(cs.st, d_enc.as<uint8_t>(), d_cols.as<uint32_t>(), N, L, nr, d_rep.as<uint8_t>()); HIPCHK(hipGetLastError()); });
           }
           cs.timed(I.ms_counts, [&] {
@@ -98,7 +96,7 @@ extern "C" int ckm_gtree_run(ckm_ctx *ctx, const ckm_gtree_args *a, uint64_t bud
       }
     }
     HIPCHK(hipStreamSynchronize(cs.st));
-    I.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    I.ms_total = t0.ms();
     if (info) *info = I;
   });
 }

@@ -23,6 +23,7 @@
 #include "ckm_internal.h"
 #include "dev_types.h"
 #include "host_pool.h"
+#include "marker_sets.h"
 #include "stream_plan.h"
 #include "cascade_plan.h"
 
@@ -236,6 +237,11 @@ struct CallStream {
     st = s;
     for (auto &e : ev) HIPCHK(hipEventCreate(&e));
   }
+  // size a buffer, then fill it from the host
+  void put(DevBuf &d, const void *src, size_t bytes) {
+    d.ensure(bytes);
+    if (bytes) HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, st));
+  }
   void mark(int k) { HIPCHK(hipEventRecord(ev[k], st)); }
   float ms(int a, int b) { float t = 0.f; HIPCHK(hipEventElapsedTime(&t, ev[a], ev[b])); return t; }      // both recorded and waited for by the caller
   // a phase between two events that the host waits for: it needs the phase's result, or reuses its buffers, before the next one
@@ -251,6 +257,20 @@ struct CallStream {
     if (own) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
   }
   CallStream() = default; CallStream(const CallStream &) = delete; CallStream &operator=(const CallStream &) = delete;
+};
+
+// The marker sets of a call on the device (marker_sets.h), for the three passes that score them: four uploads, in this order.
+struct SetsBufs {
+  DevBuf ms_off, cs_off, cs_marker, num_markers;
+  uint32_t S = 0;
+  void upload(CallStream &cs, const msets::Packed &P) {
+    cs.put(ms_off, P.ms_off.data(), P.ms_off.size() * 4);
+    cs.put(cs_off, P.cs_off.data(), P.cs_off.size() * 4);
+    cs.put(cs_marker, P.cs_marker.data(), P.cs_marker.size() * 4);
+    cs.put(num_markers, P.num_markers.data(), P.num_markers.size() * 4);
+    S = (uint32_t)P.num_markers.size();
+  }
+  msets::SetsDev dev() const { return {ms_off.as<uint32_t>(), cs_off.as<uint32_t>(), cs_marker.as<uint32_t>(), num_markers.as<uint32_t>(), S}; }
 };
 
 }  // namespace ckm

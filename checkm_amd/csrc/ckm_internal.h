@@ -1,8 +1,10 @@
 // ckm_internal.h -- shared declarations of libcheckm_hip.so (not part of the ABI).
 #pragma once
+#include <chrono>
 #include <cstdint>
 #include <cstddef>
 #include <cstdlib>
+#include <new>
 #include <string>
 #include <vector>
 #include <stdexcept>
@@ -22,6 +24,31 @@ struct Error : std::runtime_error {
 };
 
 void set_last_error(const std::string &m);
+
+// What a pass's host-side check says of a call.  The pass namespaces name the three kinds with using-declarations, and the host executors
+// of the CPU tests hand the numbers to their Python callers.
+enum { ARGS_OK = 0, ARGS_INVALID = 1, ARGS_RANGE = 2 };
+inline int kind_code(int kind) { return kind == ARGS_OK ? CKM_OK : kind == ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL; }
+// inside a guarded call: a refused call goes no further
+inline void refuse(int kind, const std::string &why) {
+  if (kind != ARGS_OK) throw Error(kind_code(kind), why);
+}
+// a ckm_*_check entry: check(why) gives the kind
+template <class Check>
+int check_entry(Check &&check) {
+  try {
+    std::string why;
+    const int kind = check(why);
+    if (kind != ARGS_OK) set_last_error(why);
+    return kind_code(kind);
+  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+}
+
+// host wall clock of a call or of a piece of one, in the milliseconds the info structs report
+struct WallClock {
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+};
 
 // The byte budget of a batched pass: what the caller asked for, or the variable's megabytes, or the default when it is unset or not positive
 inline uint64_t batch_budget(uint64_t asked, const char *env, long default_mb) {

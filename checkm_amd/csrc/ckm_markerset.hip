@@ -3,7 +3,6 @@
 // (the reported marker pairs of every query in (i, j) order).  The co-location pass runs in rounds of whole queries whose packed entries
 // and tile counts fit the byte budget -- pack, count, scan, then the fill pass in batches of whole rows whose output fits the budget --
 // so the memory of a call does not grow with the number of queries or of reported pairs, and no result depends on the budget.
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -14,8 +13,8 @@
 #include "pairs_host.h"
 
 namespace ckm {
-struct MsetTableDev { const uint8_t *cls; const uint32_t *pos_off; const int32_t *pos; uint32_t G, C; };
-struct MsetOut { const uint64_t *row_base; const uint32_t *row_total; uint64_t batch_base, cap; uint32_t *pi, *pj, *count; };
+using ms::MsetOut;
+using ms::MsetTableDev;
 void launch_mset_markers(hipStream_t st, const MsetTableDev &T, uint32_t q0, uint32_t nq, const uint64_t *qg_off, const uint32_t *qg, const double *tU, const double *tS,
                          uint8_t *flag, uint32_t *counts);
 void launch_mset_pack(hipStream_t st, const MsetTableDev &T, const ms::Query *queries, uint32_t nq, uint64_t nentries, const uint32_t *qg, const uint32_t *qm, ms::Entry *pk);
@@ -44,14 +43,6 @@ struct ckm_mset_result {
   double ms_upload = 0, ms_markers = 0, ms_pack = 0, ms_count = 0, ms_scan = 0, ms_fill = 0, ms_download = 0, ms_total = 0;
 };
 
-static void refuse(int kind, const std::string &why) {
-  if (kind != ms::ARGS_OK) throw Error(kind == ms::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL, why);
-}
-static void put(CallStream &cs, DevBuf &d, const void *src, size_t bytes) {
-  d.ensure(bytes);
-  if (bytes) HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, cs.st));
-}
-
 extern "C" int ckm_mset_table_create(ckm_ctx *ctx, uint32_t ngenomes, uint32_t nfamilies, const uint8_t *count_class, const uint64_t *pos_off, const int64_t *pos,
                                      double *ms_upload, ckm_mset_table **out) {
   CallStream cs;
@@ -70,9 +61,9 @@ extern "C" int ckm_mset_table_create(ckm_ctx *ctx, uint32_t ngenomes, uint32_t n
     for (uint64_t k = 0; k < t->npos; ++k) p[k] = (int32_t)pos[k];
     cs.open(ctx->device);
     cs.timed(t->ms_upload, [&] {
-      put(cs, t->d_cls, count_class, cells);
-      put(cs, t->d_off, off.data(), (cells + 1) * 4);
-      put(cs, t->d_pos, p.data(), t->npos * 4);
+      cs.put(t->d_cls, count_class, cells);
+      cs.put(t->d_off, off.data(), (cells + 1) * 4);
+      cs.put(t->d_pos, p.data(), t->npos * 4);
     });
     if (ms_upload) *ms_upload = t->ms_upload;
     *out = t.release();
@@ -94,7 +85,7 @@ extern "C" int ckm_mset_markers(ckm_ctx *ctx, const ckm_mset_table *t, uint32_t 
     if (t->device != ctx->device) throw Error(CKM_EINVAL, "the table lives on another device");
     std::string why;
     refuse(ms::check_queries(t->G, t->C, nqueries, qg_off, qg, nullptr, nullptr, why), why);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     budget_bytes = batch_budget(budget_bytes, "CKM_MSET_BATCH_MB", 256);
     std::unique_ptr<ckm_mset_result> o(new ckm_mset_result());
     o->nqueries = nqueries; o->nfamilies = t->C; o->has_counts = want_counts != 0;
@@ -105,10 +96,10 @@ extern "C" int ckm_mset_markers(ckm_ctx *ctx, const ckm_mset_table *t, uint32_t 
       cs.open(ctx->device);
       DevBuf d_goff, d_g, d_tu, d_ts, d_flag, d_counts;
       cs.timed(o->ms_upload, [&] {
-        put(cs, d_goff, qg_off, ((size_t)nqueries + 1) * 8);
-        put(cs, d_g, qg, qg_off[nqueries] * 4);
-        put(cs, d_tu, ubiquity_threshold, (size_t)nqueries * 8);
-        put(cs, d_ts, single_copy_threshold, (size_t)nqueries * 8);
+        cs.put(d_goff, qg_off, ((size_t)nqueries + 1) * 8);
+        cs.put(d_g, qg, qg_off[nqueries] * 4);
+        cs.put(d_tu, ubiquity_threshold, (size_t)nqueries * 8);
+        cs.put(d_ts, single_copy_threshold, (size_t)nqueries * 8);
       });
       const uint32_t step = (uint32_t)std::min<uint64_t>(65535, std::max<uint64_t>(1, budget_bytes / per_query));
       d_flag.ensure((size_t)step * C);
@@ -127,7 +118,7 @@ extern "C" int ckm_mset_markers(ckm_ctx *ctx, const ckm_mset_table *t, uint32_t 
         o->nbatches += 1;
       }
     }
-    o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ms_total = t0.ms();
     *out = o.release();
   });
 }
@@ -142,7 +133,7 @@ extern "C" int ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_
     std::string why;
     refuse(ms::check_dist(dist_threshold, why), why);
     refuse(ms::check_queries(t->G, t->C, nqueries, qg_off, qg, qm_off, qm, why), why);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     budget_bytes = batch_budget(budget_bytes, "CKM_MSET_BATCH_MB", 256);
     const uint64_t cap_pairs = ms::budget_pairs(budget_bytes);
     const int32_t D = (int32_t)dist_threshold;
@@ -161,8 +152,8 @@ extern "C" int ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_
       DevBuf d_g, d_m, d_q, d_tiles, d_pk, d_cnt;
       PairBatches pb;
       cs.timed(o->ms_upload, [&] {
-        put(cs, d_g, qg, qg_off[nqueries] * 4);
-        put(cs, d_m, qm, qm_off[nqueries] * 4);
+        cs.put(d_g, qg, qg_off[nqueries] * 4);
+        cs.put(d_m, qm, qm_off[nqueries] * 4);
       });
       ms::Round R;
       auto take = [&](const void *h_out, uint64_t n) {
@@ -178,8 +169,8 @@ extern "C" int ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_
           o->nrounds += 1;
           d_pk.ensure(R.entries * sizeof(ms::Entry)); d_cnt.ensure(R.counts * 4);
           cs.timed(o->ms_upload, [&] {
-            put(cs, d_q, R.queries.data(), (size_t)nq * sizeof(ms::Query));
-            put(cs, d_tiles, R.tiles.data(), (size_t)ntiles * sizeof(ms::Tile));
+            cs.put(d_q, R.queries.data(), (size_t)nq * sizeof(ms::Query));
+            cs.put(d_tiles, R.tiles.data(), (size_t)ntiles * sizeof(ms::Tile));
           });
           const ms::Query *dq = d_q.as<ms::Query>();
           const ms::Tile *dt = d_tiles.as<ms::Tile>();
@@ -200,21 +191,21 @@ extern "C" int ckm_mset_colocated(ckm_ctx *ctx, const ckm_mset_table *t, uint32_
                                      d_cnt.as<uint32_t>(), mo);
                  },
                  take);
-          const auto s0 = std::chrono::steady_clock::now();
+          const WallClock s0;
           for (uint32_t q = q0; q < q1; ++q) {
             const ms::Query &Q = R.queries[q - q0];
             uint64_t n = 0;
             for (uint32_t k = 0; k < Q.nrows; ++k) n += pb.row_total[Q.row_off + k];
             o->pair_off[q + 1] = o->pair_off[q] + n;
           }
-          o->ms_scan += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
+          o->ms_scan += s0.ms();
         } else {
           for (uint32_t q = q0; q < q1; ++q) o->pair_off[q + 1] = o->pair_off[q];
         }
         q0 = q1;
       }
     }
-    o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ms_total = t0.ms();
     *out = o.release();
   });
 }

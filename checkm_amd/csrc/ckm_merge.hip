@@ -2,7 +2,6 @@
 // the reported pairs in the reference's order out, as columns and / or as the lines of merger.tsv.  A count pass, a scan and a fill pass
 // per stretch of rows; the fill pass runs in batches of whole rows whose output fits the budget, so the memory of a call does not grow
 // with the number of reported pairs.
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -14,12 +13,8 @@
 #include "pairs_host.h"
 
 namespace ckm {
-struct MergeBins {
-  const uint64_t *bits; const int64_t *hit_sum; const int32_t *n_markers; double *comp, *cont; uint32_t nbins, nwords;
-};
-struct MergeOut {
-  const uint64_t *row_base; uint64_t batch_base, cap; uint32_t *pi, *pj; double *cols;
-};
+using mg::MergeBins;
+using mg::MergeOut;
 void launch_merge_bins(hipStream_t st, const MergeBins &B);
 void launch_merge_tiles(hipStream_t st, bool fill, const MergeBins &B, const mg::Thresholds &thr, uint32_t row_lo, uint32_t row_hi, uint32_t count_row0,
                         uint32_t *tile_count, const MergeOut &out);
@@ -51,7 +46,7 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
     if (append_path && !bin_ids) throw Error(CKM_EINVAL, "lines cannot be written without the bin ids");
     const std::string why = mg::check_args(nbins, ngenes, member_bits, hit_sum, n_markers, thr);
     if (!why.empty()) throw Error(CKM_EINVAL, why);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     budget_bytes = batch_budget(budget_bytes, "CKM_MERGE_BATCH_MB", 256);
     const uint64_t cap_pairs = mg::budget_pairs(budget_bytes);
     const mg::Thresholds T = {thr[0], thr[1], thr[2], thr[3]};
@@ -68,11 +63,11 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
       cs.open(ctx->device);      // every phase below is waited for (cs.timed): the host needs its result before the next one
       DevBuf d_bits, d_sum, d_n, d_stat, d_count;
       PairBatches pb;
-      d_bits.ensure(nb * nwords * 8); d_sum.ensure(nb * 8); d_n.ensure(nb * 4); d_stat.ensure(nb * 16);
+      d_stat.ensure(nb * 16);
       cs.timed(o->ms_upload, [&] {
-        HIPCHK(hipMemcpyAsync(d_bits.p, member_bits, nb * nwords * 8, hipMemcpyHostToDevice, cs.st));
-        HIPCHK(hipMemcpyAsync(d_sum.p, hit_sum, nb * 8, hipMemcpyHostToDevice, cs.st));
-        HIPCHK(hipMemcpyAsync(d_n.p, n_markers, nb * 4, hipMemcpyHostToDevice, cs.st));
+        cs.put(d_bits, member_bits, nb * nwords * 8);
+        cs.put(d_sum, hit_sum, nb * 8);
+        cs.put(d_n, n_markers, nb * 4);
       });
       const MergeBins B = {d_bits.as<uint64_t>(), d_sum.as<int64_t>(), d_n.as<int32_t>(), d_stat.as<double>(), d_stat.as<double>() + nb, nbins, nwords};
       cs.timed(o->ms_bins, [&] { launch_merge_bins(cs.st, B); HIPCHK(hipGetLastError()); });
@@ -88,7 +83,7 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
           for (int c = 0; c < mg::NCOL; ++c) o->col[c].insert(o->col[c].end(), hc + (size_t)c * n, hc + (size_t)(c + 1) * n);
         }
         if (fp) {
-          const auto w0 = std::chrono::steady_clock::now();
+          const WallClock w0;
           constexpr uint64_t STEP = 1 << 16;                 // the text of a batch is several times its columns: formatted and written in pieces
           for (uint64_t k = 0; k < n; k += STEP) {
             const uint64_t m = std::min<uint64_t>(STEP, n - k);
@@ -96,7 +91,7 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
             mg::format_lines(lines, bin_ids, hi + k, hj + k, hc + k, n, m);
             if (fwrite(lines.data(), 1, lines.size(), fp.get()) != lines.size()) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
           }
-          o->ms_write += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
+          o->ms_write += w0.ms();
         }
         o->npairs += n; o->nbatches += 1;
       };
@@ -116,7 +111,7 @@ extern "C" int ckm_merge_run(ckm_ctx *ctx, uint32_t nbins, uint32_t ngenes, cons
       }
     }
     if (fp && fclose(fp.release()) != 0) throw Error(CKM_EIO, std::string("cannot write to ") + append_path);
-    o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ms_total = t0.ms();
     *out = o.release();
   });
 }

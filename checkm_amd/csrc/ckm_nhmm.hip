@@ -2,7 +2,6 @@
 // model go up once; the tiles then go in batches whose row buffer (8 bytes per owned row) stays inside the byte budget.  Per batch: one
 // scan launch per model with tiles in it, the tiles' counts come back, the host scans them, and one fill launch writes the reported rows
 // in (tile, row) order.  The hits are formed on the host from the few rows that survive.  No result depends on the budget.
-#include <chrono>
 #include <string>
 #include <vector>
 #include "ckm_host.h"
@@ -17,10 +16,6 @@ void launch_nhmm_fill(hipStream_t st, const long long *rowbuf, const nhmm::TileD
 }  // namespace ckm
 using namespace ckm;
 
-static void put(CallStream &cs, DevBuf &d, const void *src, size_t bytes) {
-  d.ensure(bytes);
-  if (bytes) HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, cs.st));
-}
 
 extern "C" int ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucseq *b, uint64_t budget_bytes, ckm_nhmm_result **out, ckm_nhmm_info *info) {
   CallStream cs;
@@ -28,10 +23,8 @@ extern "C" int ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucs
     if (!ctx || !a || !b || !out) throw Error(CKM_EINVAL, "NULL argument");
     *out = nullptr;
     std::string why;
-    const int kind = nhmm_check_args(a, why);
-    if (kind != nhmm::ARGS_OK) throw Error(kind == nhmm::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL, why);
-    const auto t0 = std::chrono::steady_clock::now();
-    auto since = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
+    refuse(nhmm_check_args(a, why), why);
+    const WallClock t0;
     const nhmm::Args A = nhmm_args_of(a);
     const nhmm::Seqs S = {b->text.data(), b->seq_off.data(), b->seq_bytes.data(), (uint32_t)b->seq_off.size()};
     bool too_long = false;
@@ -56,12 +49,12 @@ extern "C" int ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucs
         images.insert(images.end(), img.begin(), img.end());
         img_off[m + 1] = images.size();
       }
-      I.ms_tables = since(t0);
+      I.ms_tables = t0.ms();
       cs.open(ctx->device);
       DevBuf d_text, d_img, d_tiles, d_rowbuf, d_counts, d_dst, d_otile, d_opos, d_ostart, d_oscore;
       cs.timed(I.ms_upload, [&] {
-        put(cs, d_text, b->text.data(), b->text.size());
-        put(cs, d_img, images.data(), images.size() * 4);
+        cs.put(d_text, b->text.data(), b->text.size());
+        cs.put(d_img, images.data(), images.size() * 4);
       });
       std::vector<nhmm::TileDev> td;
       std::vector<uint32_t> counts, h_tile, h_pos, h_start;
@@ -78,7 +71,7 @@ extern "C" int ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucs
           td[k] = nhmm::TileDev{S.off[t.seq], t.out_off, (uint32_t)S.bytes[t.seq], t.first, t.own, t.last, t.strand, t.model, A.min_score[t.model], 0};
           I.cells += nhmm::tile_cells(A, t);
         }
-        cs.timed(I.ms_upload, [&] { put(cs, d_tiles, td.data(), nt * sizeof(nhmm::TileDev)); });
+        cs.timed(I.ms_upload, [&] { cs.put(d_tiles, td.data(), nt * sizeof(nhmm::TileDev)); });
         d_rowbuf.ensure(nrows * 8); d_counts.ensure(nt * 4);
         cs.timed(I.ms_scan, [&] {
           for (size_t k = 0, z; k < nt; k = z) {      // the tiles of one model are consecutive
@@ -100,7 +93,7 @@ extern "C" int ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucs
             dst[k] = total; total += counts[k];
           }
           if (total) {
-            put(cs, d_dst, dst.data(), nt * 8);
+            cs.put(d_dst, dst.data(), nt * 8);
             d_otile.ensure(total * 4); d_opos.ensure(total * 4); d_ostart.ensure(total * 4); d_oscore.ensure(total * 4);
             launch_nhmm_fill(cs.st, d_rowbuf.as<long long>(), d_tiles.as<nhmm::TileDev>(), d_dst.as<uint64_t>(), (uint32_t)nt, d_otile.as<uint32_t>(), d_opos.as<uint32_t>(),
                              d_ostart.as<uint32_t>(), d_oscore.as<int32_t>());
@@ -125,11 +118,11 @@ extern "C" int ckm_nhmm_run(ckm_ctx *ctx, const ckm_nhmm_args *a, const ckm_nucs
         }
         ++I.batches;
       }
-      const auto th = std::chrono::steady_clock::now();
+      const WallClock th;
       nhmm::hits_host(S, R->rows, R->hits);
-      I.ms_hits = since(th);
+      I.ms_hits = th.ms();
     }
-    I.ms_total = since(t0);
+    I.ms_total = t0.ms();
     if (info) *info = I;
     *out = R.release();
   });

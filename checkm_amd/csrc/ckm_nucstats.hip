@@ -1,6 +1,5 @@
 // ckm_nucstats.hip -- C ABI of the nucleotide statistics pass (kernels_nucstats.hip): a batch read by ckm_nucseq_read in, per-sequence base
 // counts, contig pieces and (optionally) canonical 4-mer counts out.  Count pass, scan of the per-tile run starts on the host, fill pass.
-#include <chrono>
 #include <memory>
 #include <vector>
 #include "ckm_host.h"
@@ -28,7 +27,7 @@ extern "C" int ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, ui
     if (tile_bytes == 0) tile_bytes = 4096;                 // measured best of 4, 16, 64, 256 KiB (DESIGN.md section "Bin statistics")
     if (tile_bytes % ns::LANE_BYTES || tile_bytes > (1u << 20)) throw Error(CKM_EINVAL, "tile_bytes must be a multiple of 16 and at most 1 MiB");
     *out = nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     cs.open(ctx->device);
     const uint32_t nseq = (uint32_t)b->seq_off.size();
     std::unique_ptr<ckm_nucstats> o(new ckm_nucstats());
@@ -39,13 +38,13 @@ extern "C" int ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, ui
     uint8_t canon[256];
     ns::canonical_table(canon);
     DevBuf d_text, d_tiles, d_canon, d_cnt, d_tetra, d_evoff, d_base, d_ev;
-    d_text.ensure(b->text.size()); d_tiles.ensure(std::max<size_t>(1, nt) * sizeof(ns::Tile)); d_canon.ensure(256);
+    d_tiles.ensure(std::max<size_t>(1, nt) * sizeof(ns::Tile));
     d_cnt.ensure(std::max<size_t>(1, nt) * ns::NCOUNT * 4);
     if (tetra) d_tetra.ensure(std::max<size_t>(1, nseq) * ns::NKMER * 4);
     cs.mark(0);
-    HIPCHK(hipMemcpyAsync(d_text.p, b->text.data(), b->text.size(), hipMemcpyHostToDevice, cs.st));
+    cs.put(d_text, b->text.data(), b->text.size());
     if (nt) HIPCHK(hipMemcpyAsync(d_tiles.p, tiles.data(), nt * sizeof(ns::Tile), hipMemcpyHostToDevice, cs.st));
-    HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, cs.st));
+    cs.put(d_canon, canon, 256);
     if (tetra) HIPCHK(hipMemsetAsync(d_tetra.p, 0, std::max<size_t>(1, nseq) * ns::NKMER * 4, cs.st));
     cs.mark(1);
     launch_nucstats_count(cs.st, d_text.as<uint8_t>(), d_tiles.as<ns::Tile>(), nt, d_canon.as<uint8_t>(), d_cnt.as<uint32_t>(), tetra ? d_tetra.as<uint32_t>() : nullptr);
@@ -64,9 +63,9 @@ extern "C" int ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, ui
     std::vector<uint64_t> evs(nev);
     float ms_fill = 0.f;
     if (nev) {
-      d_evoff.ensure(ev_off.size() * 8); d_base.ensure(nonn_base.size() * 8); d_ev.ensure(nev * 8);
-      HIPCHK(hipMemcpyAsync(d_evoff.p, ev_off.data(), ev_off.size() * 8, hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_base.p, nonn_base.data(), nonn_base.size() * 8, hipMemcpyHostToDevice, cs.st));
+      d_ev.ensure(nev * 8);
+      cs.put(d_evoff, ev_off.data(), ev_off.size() * 8);
+      cs.put(d_base, nonn_base.data(), nonn_base.size() * 8);
       cs.mark(3);
       launch_nucstats_fill(cs.st, d_text.as<uint8_t>(), d_tiles.as<ns::Tile>(), nt, d_evoff.as<uint64_t>(), d_base.as<uint64_t>(), d_ev.as<uint64_t>());
       HIPCHK(hipGetLastError());
@@ -78,7 +77,7 @@ extern "C" int ckm_nucstats_run(ckm_ctx *ctx, const ckm_nucseq *b, int tetra, ui
     ns::assemble(tiles, cnt.data(), ev_off, evs.data(), nseq, o->count, o->piece_off, o->piece_len);
     o->ms_upload = cs.ms(0, 1); o->ms_count = cs.ms(1, 2); o->ms_fill = ms_fill;
     o->bytes = b->text.size(); o->tiles = nt; o->run_starts = nev;
-    o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ms_total = t0.ms();
     *out = o.release();
   });
 }

@@ -2,7 +2,6 @@
 // tetranucleotide profile and its coding bases in; per-sequence GC, coding density, tetranucleotide distance, their differences to the bin
 // and the outlier flags out.  Integer sums per bin on the host, four kernels, one download.
 #include <algorithm>
-#include <chrono>
 #include <memory>
 #include <numeric>
 #include <string>
@@ -35,7 +34,7 @@ extern "C" int ckm_outliers_run(ckm_ctx *ctx, const ckm_nucseq *b, const uint64_
   return guarded([&] {
     if (!ctx || !b || !count || !sig || !coding_per_seq || !bounds || !zero_seq || !out) throw Error(CKM_EINVAL, "NULL argument");
     *out = nullptr; *zero_seq = -1;
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     const uint32_t nseq = (uint32_t)b->seq_off.size(), nbins = (uint32_t)b->file_first.size() - 1;
     // the bound tables: every index inside its array, no empty table (the kernels read key[0] of the table they are given)
     const ckm_outlier_bounds &B = *bounds;
@@ -74,18 +73,16 @@ extern "C" int ckm_outliers_run(ckm_ctx *ctx, const ckm_nucseq *b, const uint64_
       cs.open(ctx->device);
       DevBuf d_count, d_sig, d_coding, d_seqbin, d_first, d_order, d_sum, d_seq, d_flags, d_mean, d_binsig, d_tab, d_tabidx;
       const size_t n = nseq;
-      d_count.ensure(n * 64); d_sig.ensure(n * ol::NSIG * 8); d_coding.ensure(n * 8); d_seqbin.ensure(n * 4);
-      d_first.ensure(((size_t)nbins + 1) * 4); d_order.ensure((size_t)nbins * 4); d_sum.ensure((size_t)nbins * 32);
       d_seq.ensure(n * 48); d_flags.ensure(n); d_mean.ensure((size_t)nbins * 16); d_binsig.ensure((size_t)nbins * ol::NSIG * 8);
       d_tab.ensure((size_t)nrows * 24 + ((size_t)B.ntables + 1) * 4 + 8); d_tabidx.ensure((size_t)nbins * 8);
       cs.mark(0);
-      HIPCHK(hipMemcpyAsync(d_count.p, count, n * 64, hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_sig.p, sig, n * ol::NSIG * 8, hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_coding.p, coding_per_seq, n * 8, hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_seqbin.p, seq_bin.data(), n * 4, hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_first.p, b->file_first.data(), ((size_t)nbins + 1) * 4, hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_order.p, order.data(), (size_t)nbins * 4, hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_sum.p, bin_sum.data(), (size_t)nbins * 32, hipMemcpyHostToDevice, cs.st));
+      cs.put(d_count, count, n * 64);
+      cs.put(d_sig, sig, n * ol::NSIG * 8);
+      cs.put(d_coding, coding_per_seq, n * 8);
+      cs.put(d_seqbin, seq_bin.data(), n * 4);
+      cs.put(d_first, b->file_first.data(), ((size_t)nbins + 1) * 4);
+      cs.put(d_order, order.data(), (size_t)nbins * 4);
+      cs.put(d_sum, bin_sum.data(), (size_t)nbins * 32);
       // tables: key, lo, hi (nrows doubles each), then tab_off
       double *tk = d_tab.as<double>();
       HIPCHK(hipMemcpyAsync(tk, B.key, (size_t)nrows * 8, hipMemcpyHostToDevice, cs.st));
@@ -121,7 +118,7 @@ extern "C" int ckm_outliers_run(ckm_ctx *ctx, const ckm_nucseq *b, const uint64_
       HIPCHK(hipStreamSynchronize(cs.st));
       o->ms_upload = cs.ms(0, 1); o->ms_seq = cs.ms(1, 2); o->ms_binsig = cs.ms(2, 3); o->ms_td = cs.ms(3, 4); o->ms_flags = cs.ms(4, 5);
     }
-    o->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    o->ms_total = t0.ms();
     *out = o.release();
   });
 }

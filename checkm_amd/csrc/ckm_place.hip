@@ -3,7 +3,6 @@
 // within the byte budget.  Per chunk: the upward and the downward sweep level by level, the edge tables, the scan, whose (query, edge)
 // products stay on the device between chunks.  Then the best edges of every query, and a second walk over the chunks for the grid of
 // every kept pair (the partials are recomputed; a call of one chunk keeps them).  No result depends on the budget.
-#include <chrono>
 #include <string>
 #include <vector>
 #include "ckm_host.h"
@@ -25,10 +24,6 @@ void launch_place_best(hipStream_t st, const place::PlaceDev &T);
 }  // namespace ckm
 using namespace ckm;
 
-static void put(CallStream &cs, DevBuf &d, const void *src, size_t bytes) {
-  d.ensure(bytes);
-  if (bytes) HIPCHK(hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, cs.st));
-}
 
 extern "C" int ckm_place_run(ckm_ctx *ctx, const ckm_place_args *a, uint64_t budget_bytes, const ckm_place_out *out, ckm_place_info *info) {
   CallStream cs;
@@ -36,13 +31,12 @@ extern "C" int ckm_place_run(ckm_ctx *ctx, const ckm_place_args *a, uint64_t bud
     if (!ctx || !a || !out) throw Error(CKM_EINVAL, "NULL argument");
     std::string why;
     place::Schedule sch;
-    const int kind = place_check_args(a, sch, why);
-    if (kind != place::ARGS_OK) throw Error(kind == place::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL, why);
+    refuse(place_check_args(a, sch, why), why);
     const uint32_t N = a->nnodes, R = a->nrates, S = a->nsites, NQy = a->nqueries, F = a->nfrac, G = a->npend, KP_ = a->max_pitches, E = N - 1;
     const uint32_t Keff = std::min(KP_, E);
     const size_t nout = (size_t)NQy * KP_;
     if (nout && (!out->top_edge || !out->scan_m || !out->scan_e || !out->ref_m || !out->ref_e || !out->ref_f || !out->ref_g)) throw Error(CKM_EINVAL, "NULL argument");
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     budget_bytes = batch_budget(budget_bytes, "CKM_PLACE_BATCH_MB", 2048);
     const uint32_t C = place::chunk_sites(S, N, R, budget_bytes);
     ckm_place_info I = {};
@@ -52,28 +46,28 @@ extern "C" int ckm_place_run(ckm_ctx *ctx, const ckm_place_args *a, uint64_t bud
       std::vector<uint8_t> rowcode((size_t)a->nrows * S), qcode((size_t)NQy * S);
       for (uint32_t k = 0; k < a->nrows; ++k) for (uint32_t s = 0; s < S; ++s) rowcode[(size_t)k * S + s] = place::code_of(a->rows[a->row_off[k] + s]);
       for (uint32_t k = 0; k < NQy; ++k) for (uint32_t s = 0; s < S; ++s) qcode[(size_t)k * S + s] = place::code_of(a->queries[a->q_off[k] + s]);
-      I.ms_pack = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      I.ms_pack = t0.ms();
       cs.open(ctx->device);
       DevBuf d_coff, d_child, d_parent, d_leafrow, d_rowcode, d_qcode, d_w, d_pi, d_U, d_Ui, d_elen, d_ehalf, d_edist, d_epend, d_up, d_down, d_edges;
       DevBuf d_Plen, d_Phalf, d_Pdist, d_Ppend, d_D, d_X, d_T, d_dexp, d_xexp, d_texp, d_accm, d_acce, d_raccm, d_racce, d_top, d_sm, d_se, d_rm, d_re, d_rf, d_rg, d_rootv, d_rootexp;
       cs.timed(I.ms_upload, [&] {
-        put(cs, d_coff, a->child_off, ((size_t)N + 1) * 8);
-        put(cs, d_child, a->child, (size_t)E * 4);
-        put(cs, d_parent, sch.parent.data(), (size_t)N * 4);
-        put(cs, d_leafrow, sch.leaf_row.data(), (size_t)N * 4);
-        put(cs, d_rowcode, rowcode.data(), rowcode.size());
-        put(cs, d_qcode, qcode.data(), qcode.size());
-        put(cs, d_w, a->weights, (size_t)R * 8);
-        put(cs, d_pi, a->pi, place::NS * 8);
-        put(cs, d_U, a->U, place::PM * 8);
-        put(cs, d_Ui, a->Uinv, place::PM * 8);
-        put(cs, d_elen, a->exp_len, (size_t)N * R * place::NS * 8);
-        put(cs, d_ehalf, a->exp_half, (size_t)N * R * place::NS * 8);
-        put(cs, d_edist, a->exp_dist, (size_t)N * F * 2 * R * place::NS * 8);
-        put(cs, d_epend, a->exp_pend, ((size_t)G + 1) * R * place::NS * 8);
-        put(cs, d_up, sch.up_nodes.data(), (size_t)N * 4);
-        put(cs, d_down, sch.down_nodes.data(), (size_t)E * 4);
-        put(cs, d_edges, sch.edges.data(), (size_t)E * 4);
+        cs.put(d_coff, a->child_off, ((size_t)N + 1) * 8);
+        cs.put(d_child, a->child, (size_t)E * 4);
+        cs.put(d_parent, sch.parent.data(), (size_t)N * 4);
+        cs.put(d_leafrow, sch.leaf_row.data(), (size_t)N * 4);
+        cs.put(d_rowcode, rowcode.data(), rowcode.size());
+        cs.put(d_qcode, qcode.data(), qcode.size());
+        cs.put(d_w, a->weights, (size_t)R * 8);
+        cs.put(d_pi, a->pi, place::NS * 8);
+        cs.put(d_U, a->U, place::PM * 8);
+        cs.put(d_Ui, a->Uinv, place::PM * 8);
+        cs.put(d_elen, a->exp_len, (size_t)N * R * place::NS * 8);
+        cs.put(d_ehalf, a->exp_half, (size_t)N * R * place::NS * 8);
+        cs.put(d_edist, a->exp_dist, (size_t)N * F * 2 * R * place::NS * 8);
+        cs.put(d_epend, a->exp_pend, ((size_t)G + 1) * R * place::NS * 8);
+        cs.put(d_up, sch.up_nodes.data(), (size_t)N * 4);
+        cs.put(d_down, sch.down_nodes.data(), (size_t)E * 4);
+        cs.put(d_edges, sch.edges.data(), (size_t)E * 4);
       });
       const size_t part = (size_t)N * R * place::NS * C, npairs = (size_t)NQy * Keff;
       d_Plen.ensure((size_t)N * R * place::PM * 8); d_Phalf.ensure((size_t)N * R * place::PM * 8); d_Pdist.ensure((size_t)N * F * 2 * R * place::PM * 8);
@@ -145,7 +139,7 @@ extern "C" int ckm_place_run(ckm_ctx *ctx, const ckm_place_args *a, uint64_t bud
           }
       });
     }
-    I.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    I.ms_total = t0.ms();
     if (info) *info = I;
   });
 }

@@ -2,7 +2,6 @@
 // windows (start, size) of its scaffold in; per window two counters (GC, CD) or the tetranucleotide distance to the genome's signature
 // (TD) out, and the totals of the scaffold.  The scaffold is joined on the host while the upload buffer is filled and goes up once; the
 // prefix rows stay on the device; the 136-count rows of the TD windows go through seqwin_td_kernel in batches that fit a byte budget.
-#include <chrono>
 #include <cstdlib>
 #include <vector>
 #include "ckm_host.h"
@@ -34,13 +33,13 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
       if (b->seq_cp[s] != b->seq_bytes[s]) throw Error(CKM_EINVAL, "sequence " + b->ids[s] + " holds non-ASCII characters: its scaffold is not taken");
     if (block == 0) block = rd::DEFAULT_BLOCK;
     budget_bytes = batch_budget(budget_bytes, "CKM_NUCSTATS_BATCH_MB", 1024);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     *timing = ckm_refdist_timing{};
     std::vector<uint8_t> text;
     rd::join_scaffold(b->text.data(), b->seq_off.data(), b->seq_bytes.data(), nseq, sep_len, text);
     std::vector<uint32_t> s32((size_t)std::max<uint64_t>(1, nwin)), w32((size_t)std::max<uint64_t>(1, nwin));
     for (uint64_t x = 0; x < nwin; ++x) { s32[x] = (uint32_t)starts[x]; w32[x] = (uint32_t)sizes[x]; }
-    timing->ms_scaffold = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timing->ms_scaffold = t0.ms();
     const uint32_t nblocks = (uint32_t)((L + block - 1) / block), ncol = rd::ncol_of(stat);
     const size_t row_bytes = (size_t)ncol * 4, rows_bytes = ((size_t)nblocks + 1) * row_bytes;
     const uint64_t max_windows = std::max<uint64_t>(1, std::min<uint64_t>(budget_bytes / rd::TD_ROW_BYTES, rd::MAX_WINDOWS));
@@ -50,15 +49,14 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
     uint8_t canon[256];
     ns::canonical_table(canon);
     DevBuf d_text, d_canon, d_rows, d_starts, d_sizes, d_cnt, d_tet, d_td, d_file, d_sig;
-    d_text.ensure(text.size()); d_canon.ensure(256); d_rows.ensure(rows_bytes);
-    d_starts.ensure(s32.size() * 4); d_sizes.ensure(w32.size() * 4);
-    if (td) { d_tet.ensure(scratch_rows * rd::TD_ROW_BYTES); d_td.ensure(s32.size() * 8); d_file.ensure(scratch_rows * 4); d_sig.ensure(ol::NSIG * 8); }
+    d_rows.ensure(rows_bytes);
+    if (td) { d_tet.ensure(scratch_rows * rd::TD_ROW_BYTES); d_td.ensure(s32.size() * 8); d_file.ensure(scratch_rows * 4); }
     else d_cnt.ensure(s32.size() * 8);
     cs.mark(0);
-    HIPCHK(hipMemcpyAsync(d_text.p, text.data(), text.size(), hipMemcpyHostToDevice, cs.st));
-    HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, cs.st));
-    HIPCHK(hipMemcpyAsync(d_starts.p, s32.data(), s32.size() * 4, hipMemcpyHostToDevice, cs.st));
-    HIPCHK(hipMemcpyAsync(d_sizes.p, w32.data(), w32.size() * 4, hipMemcpyHostToDevice, cs.st));
+    cs.put(d_text, text.data(), text.size());
+    cs.put(d_canon, canon, 256);
+    cs.put(d_starts, s32.data(), s32.size() * 4);
+    cs.put(d_sizes, w32.data(), w32.size() * 4);
     if (td) HIPCHK(hipMemsetAsync(d_file.p, 0, scratch_rows * 4, cs.st));      // every window is compared with signature 0: the genome's
     cs.mark(1);
     launch_refdist_blocks(cs.st, d_text.as<uint8_t>(), L, block, nblocks, td ? 1 : 0, d_canon.as<uint8_t>(), d_rows.as<uint32_t>());
@@ -79,7 +77,7 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
       for (int k = 0; k < rd::NKMER; ++k) { out_totals[2 + k] = totals[k]; sum += totals[k]; }
       double sig[ol::NSIG];
       for (int k = 0; k < ol::NSIG; ++k) sig[k] = ol::ratio((uint64_t)totals[k], sum);
-      HIPCHK(hipMemcpyAsync(d_sig.p, sig, sizeof(sig), hipMemcpyHostToDevice, cs.st));
+      cs.put(d_sig, sig, sizeof(sig));
       HIPCHK(hipStreamSynchronize(cs.st));
     } else {
       out_totals[0] = totals[0]; out_totals[1] = totals[1];
@@ -107,6 +105,6 @@ extern "C" int ckm_refdist_run(ckm_ctx *ctx, const ckm_nucseq *b, int stat, uint
     HIPCHK(hipStreamSynchronize(cs.st));
     timing->ms_download += cs.ms(0, 1);
     timing->windows = nwin; timing->blocks = nblocks; timing->bytes = L;
-    timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timing->ms_total = t0.ms();
   });
 }

@@ -1,7 +1,6 @@
 // ckm_seqwin.hip -- C ABI of the sequence-window pass (kernels_seqwin.hip): a batch read by ckm_nucseq_read in; per window the base
 // counts and the tetranucleotide distance to its file's bin signature out, per sequence the base counts.  The text goes up once; the
 // windows go through the device in batches whose 136-count rows fit a byte budget, and only four uint32 and one double per window stay.
-#include <chrono>
 #include <cstdlib>
 #include <vector>
 #include "ckm_host.h"
@@ -27,7 +26,7 @@ extern "C" int ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t wi
     if (piece_bytes == 0) piece_bytes = sw::DEFAULT_PIECE;
     if (piece_bytes < sw::MIN_PIECE || piece_bytes > (1u << 20)) throw Error(CKM_EINVAL, "piece_bytes must be between 16 and 1 MiB");
     budget_bytes = batch_budget(budget_bytes, "CKM_NUCSTATS_BATCH_MB", 1024);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     *timing = ckm_seq_windows_timing{};
     const uint32_t nseq = (uint32_t)b->seq_off.size(), nfiles = (uint32_t)b->file_first.size() - 1;
     const uint64_t w = (uint64_t)window_size;
@@ -56,12 +55,12 @@ extern "C" int ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t wi
       ns::canonical_table(canon);
       const size_t scratch_rows = (size_t)std::min<uint64_t>(max_windows, std::max<uint64_t>(1, nwin));
       DevBuf d_text, d_canon, d_cnt, d_td, d_tet, d_binsig, d_pieces, d_file;
-      d_text.ensure(b->text.size()); d_canon.ensure(256); d_cnt.ensure((size_t)nrows * 16);
+      d_cnt.ensure((size_t)nrows * 16);
       if (tetra) d_tet.ensure(scratch_rows * sw::ROW_BYTES);
       if (out_td) { d_td.ensure(std::max<size_t>(1, nwin) * 8); d_binsig.ensure(std::max<size_t>(1, nfiles) * ol::NSIG * 8); }
       cs.mark(0);
-      HIPCHK(hipMemcpyAsync(d_text.p, b->text.data(), b->text.size(), hipMemcpyHostToDevice, cs.st));
-      HIPCHK(hipMemcpyAsync(d_canon.p, canon, 256, hipMemcpyHostToDevice, cs.st));
+      cs.put(d_text, b->text.data(), b->text.size());
+      cs.put(d_canon, canon, 256);
       HIPCHK(hipMemsetAsync(d_cnt.p, 0, (size_t)nrows * 16, cs.st));
       if (out_td && nfiles) HIPCHK(hipMemcpyAsync(d_binsig.p, bin_sig, (size_t)nfiles * ol::NSIG * 8, hipMemcpyHostToDevice, cs.st));
       cs.mark(1);
@@ -104,6 +103,6 @@ extern "C" int ckm_seq_windows_run(ckm_ctx *ctx, const ckm_nucseq *b, int64_t wi
     if (nwin) memcpy(out_base_counts, cnt.data(), (size_t)nwin * 16);
     sw::seq_counts(cnt.data(), first.data(), nseq, out_seq_counts);
     timing->windows = nwin; timing->bytes = b->text.size(); timing->skipped_seqs = skipped;
-    timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timing->ms_total = t0.ms();
   });
 }

@@ -1,7 +1,6 @@
 // ckm_unbinned.hip -- C ABI of the selective base count of `checkm unbinned` (kernels_unbinned.hip): a batch read by ckm_nucseq_read and a
 // keep flag per sequence in; A, C, G, T+U and the code points of every kept sequence out.  Only the tiles of kept sequences travel: their
 // padded text is packed into batches of a byte budget, the tile rows of all batches stay on the device and are summed per sequence at the end.
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -23,7 +22,7 @@ extern "C" int ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *b, const uint8
     if (tile_bytes == 0) tile_bytes = ub::DEFAULT_TILE;
     if (tile_bytes % ub::WAVE_BYTES || tile_bytes > ub::MAX_TILE) throw Error(CKM_EINVAL, "tile_bytes must be a multiple of 1024 and at most 1 MiB");
     budget_bytes = batch_budget(budget_bytes, "CKM_NUCSTATS_BATCH_MB", 1024);
-    const auto t0 = std::chrono::steady_clock::now();
+    const WallClock t0;
     *timing = ckm_unbinned_timing{};
     const uint32_t nseq = (uint32_t)b->seq_off.size();
     if (nseq) memset(counts, 0, (size_t)nseq * ub::NCOUNT * 8);
@@ -47,17 +46,16 @@ extern "C" int ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *b, const uint8
         for (const ub::Tile &T : B.tiles)
           if (T.start % ub::LANE_BYTES || T.start + ub::pad16(T.len) > B.bytes) throw Error(CKM_EINVAL, "internal: a tile leaves its batch");
         const char *src = b->text.data() + B.spans[0].src;      // one run of the reader's text goes up as it lies
-        const auto s0 = std::chrono::steady_clock::now();
+        const WallClock s0;
         if (B.spans.size() > 1) {
           stage.resize(B.bytes);
           for (const ub::Span &S : B.spans) memcpy(stage.data() + S.dst, b->text.data() + S.src, S.bytes);
           src = stage.data();
         }
-        timing->ms_stage += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
-        d_text.ensure(B.bytes); d_tiles.ensure((size_t)nt * sizeof(ub::Tile));
+        timing->ms_stage += s0.ms();
         cs.mark(0);
-        HIPCHK(hipMemcpyAsync(d_text.p, src, B.bytes, hipMemcpyHostToDevice, cs.st));
-        HIPCHK(hipMemcpyAsync(d_tiles.p, B.tiles.data(), (size_t)nt * sizeof(ub::Tile), hipMemcpyHostToDevice, cs.st));
+        cs.put(d_text, src, B.bytes);
+        cs.put(d_tiles, B.tiles.data(), (size_t)nt * sizeof(ub::Tile));
         cs.mark(1);
         launch_unbinned_count(cs.st, d_text.as<uint8_t>(), d_tiles.as<ub::Tile>(), nt, d_rows.as<uint32_t>() + B.t0 * ub::NCOUNT);
         HIPCHK(hipGetLastError());
@@ -67,9 +65,9 @@ extern "C" int ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *b, const uint8
         timing->ms_count += cs.ms(1, 2);
         timing->batches += 1; timing->bytes += B.bytes;
       }
-      d_first.ensure(first_tile.size() * 8); d_out.ensure((size_t)nkept * ub::NCOUNT * 8);
+      d_out.ensure((size_t)nkept * ub::NCOUNT * 8);
       std::vector<uint64_t> out((size_t)nkept * ub::NCOUNT);
-      HIPCHK(hipMemcpyAsync(d_first.p, first_tile.data(), first_tile.size() * 8, hipMemcpyHostToDevice, cs.st));
+      cs.put(d_first, first_tile.data(), first_tile.size() * 8);
       cs.mark(0);
       launch_unbinned_sum(cs.st, d_rows.as<uint32_t>(), d_first.as<uint64_t>(), nkept, d_out.as<uint64_t>());
       HIPCHK(hipGetLastError());
@@ -81,6 +79,6 @@ extern "C" int ckm_unbinned_count(ckm_ctx *ctx, const ckm_nucseq *b, const uint8
       timing->ms_download = cs.ms(1, 2);
       for (uint32_t k = 0; k < nkept; ++k) memcpy(counts + (size_t)kept[k] * ub::NCOUNT, &out[(size_t)k * ub::NCOUNT], ub::NCOUNT * 8);
     }
-    timing->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    timing->ms_total = t0.ms();
   });
 }

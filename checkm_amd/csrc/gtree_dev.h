@@ -28,6 +28,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include "ckm_internal.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define GT_HD __host__ __device__ __forceinline__
@@ -46,7 +47,9 @@ constexpr int TILE = 64;                            // rows of a tile of the cou
 constexpr int CHUNK = 128;                          // bytes of a row a tile holds in LDS at once
 constexpr uint32_t NCLASS = 20;
 enum { MODEL_KIMURA = 0, MODEL_POISSON = 1, MODEL_P = 2 };
-enum { ARGS_OK = 0, ARGS_INVALID = 1, ARGS_RANGE = 2 };
+using ckm::ARGS_INVALID;
+using ckm::ARGS_OK;
+using ckm::ARGS_RANGE;
 
 // 0x80 | class of a residue, 0 of anything else
 GT_HD uint8_t encode(uint8_t c) {

@@ -18,18 +18,11 @@ int gtree_check_args(const ckm_gtree_args *a, std::string &why) {
 }  // namespace ckm
 
 extern "C" int ckm_gtree_check(const ckm_gtree_args *a) {
-  try {
-    std::string why;
-    const int kind = gtree_check_args(a, why);
-    if (kind == gtree::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == gtree::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  return check_entry([&](std::string &why) { return gtree_check_args(a, why); });
 }
 
 extern "C" int ckm_gtree_host(const ckm_gtree_args *a, uint64_t budget_bytes, const ckm_gtree_out *out, ckm_gtree_info *info) {
-  try {
-    std::string why;
+  return check_entry([&](std::string &why) {
     int kind = gtree_check_args(a, why);
     if (kind == gtree::ARGS_OK && (!out || (out->compared && !out->differ) || (out->merge_ij && !out->merge_len))) { kind = gtree::ARGS_INVALID; why = "NULL argument"; }
     if (kind == gtree::ARGS_OK) {
@@ -38,8 +31,6 @@ extern "C" int ckm_gtree_host(const ckm_gtree_args *a, uint64_t budget_bytes, co
                              counts, why);
       if (kind == gtree::ARGS_OK && info) { *info = ckm_gtree_info(); info->nrounds = counts[0]; info->ntrees = counts[1]; }
     }
-    if (kind == gtree::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == gtree::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+    return kind;
+  });
 }

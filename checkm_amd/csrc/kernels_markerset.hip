@@ -24,20 +24,6 @@
 namespace ckm {
 using namespace ms;
 
-struct MsetTableDev {
-  const uint8_t *cls;          // [G * C]
-  const uint32_t *pos_off;     // [G * C + 1]
-  const int32_t *pos;
-  uint32_t G, C;
-};
-
-struct MsetOut {
-  const uint64_t *row_base;    // [rows of the round]: reported pairs of the rows before
-  const uint32_t *row_total;   // [rows of the round]: reported pairs of the row
-  uint64_t batch_base, cap;    // first pair of this output batch; pairs the columns hold
-  uint32_t *pi, *pj, *count;   // [cap]
-};
-
 __global__ __launch_bounds__(THREADS) void mset_markers_kernel(MsetTableDev T, uint32_t q0, const uint64_t *__restrict__ qg_off, const uint32_t *__restrict__ qg,
                                                                 const double *__restrict__ tU, const double *__restrict__ tS, uint8_t *__restrict__ flag,
                                                                 uint32_t *__restrict__ counts) {

@@ -22,21 +22,6 @@
 namespace ckm {
 using namespace mg;
 
-struct MergeBins {
-  const uint64_t *bits;        // [nbins * nwords]
-  const int64_t *hit_sum;      // [nbins]
-  const int32_t *n_markers;    // [nbins]
-  double *comp, *cont;         // [nbins]
-  uint32_t nbins, nwords;
-};
-
-struct MergeOut {
-  const uint64_t *row_base;    // [rows of the count pass]: reported pairs of the rows before
-  uint64_t batch_base, cap;    // first pair of this output batch; pairs the columns hold
-  uint32_t *pi, *pj;           // [cap]
-  double *cols;                // [NCOL * cap]
-};
-
 __global__ __launch_bounds__(256) void merge_bins_kernel(MergeBins B) {
   const uint32_t b = blockIdx.x * 256u + threadIdx.x;
   if (b >= B.nbins) return;

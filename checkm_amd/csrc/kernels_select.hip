@@ -21,18 +21,6 @@
 namespace ckm {
 using namespace sel;
 
-struct SelectDev {
-  const int64_t *genome_len;    // [G]
-  const uint32_t *ncontigs;     // [G]
-  const uint64_t *row_off;      // [G + 1]
-  const uint32_t *key_off;      // [G * U + 1]
-  const int32_t *key;
-  const uint32_t *ms_off;       // [S + 1]
-  const uint32_t *cs_off, *cs_marker, *num_markers;
-  uint32_t U, S, R;
-  Params P;
-};
-
 // The bin that holds rank k (1-based) of the histogram: every lane of every wavefront returns the same.  before: entries in lower bins.
 __device__ __forceinline__ uint32_t bin_of_rank(const uint32_t *hist, uint32_t k, uint32_t &before, uint32_t &inside) {
   const int lane = threadIdx.x & (WAVE - 1);
@@ -121,8 +109,7 @@ __global__ __launch_bounds__(THREADS) void select_kernel(SelectDev T, uint32_t d
   __syncthreads();                                              // the counts, in LDS or in the block's own scratch row
 
   if (threadIdx.x == 0) { truth[(uint64_t)blockIdx.x * 2] = plan.true_comp; truth[(uint64_t)blockIdx.x * 2 + 1] = plan.true_cont; }
-  const sim::SetsDev M = {T.ms_off, T.cs_off, T.cs_marker, T.num_markers, T.S};
-  sim::score_sets(M, counts, out + (uint64_t)blockIdx.x * T.S * 4);
+  sim::score_sets(T.sets, counts, out + (uint64_t)blockIdx.x * T.sets.S * 4);
 }
 
 void launch_select(hipStream_t st, const SelectDev &T, uint32_t max_contigs, uint32_t d0, uint32_t nd, uint64_t row_base, double *truth, double *out, uint32_t *scratch,

@@ -21,14 +21,6 @@
 namespace ckm {
 using namespace sim;
 
-struct SimDev {
-  const uint32_t *key_off;      // [U + 1]
-  const int32_t *key;
-  const uint32_t *ms_off;       // [S + 1]
-  const uint32_t *cs_off, *cs_marker, *num_markers;      // num_markers [S]
-  uint32_t U, S;
-};
-
 // replicate r0 + blockIdx.x of the call; starts holds the round's starts, the first of them being entry start_base of the call's list;
 // scratch [blocks][U] only when U > STAGE_COUNTS; out [blocks][S][4]
 __global__ __launch_bounds__(THREADS) void sim_kernel(SimDev T, uint32_t r0, const uint64_t *__restrict__ rs_off, uint64_t start_base, const int32_t *__restrict__ starts,
@@ -48,14 +40,12 @@ __global__ __launch_bounds__(THREADS) void sim_kernel(SimDev T, uint32_t r0, con
   const int32_t len = contig_len[r];
   for (uint32_t m = threadIdx.x; m < T.U; m += THREADS) counts[m] = marker_count(T.key, T.key_off[m], T.key_off[m + 1], s, n, len);
   __syncthreads();                                              // the counts, in LDS or in the block's own scratch row
-
-  const SetsDev M = {T.ms_off, T.cs_off, T.cs_marker, T.num_markers, T.S};
-  score_sets(M, counts, out + (uint64_t)blockIdx.x * T.S * 4);
+  score_sets(T.sets, counts, out + (uint64_t)blockIdx.x * T.sets.S * 4);
 }
 
 void launch_sim(hipStream_t st, const SimDev &T, uint32_t r0, uint32_t nr, const uint64_t *rs_off, uint64_t start_base, const int32_t *starts, const int32_t *contig_len,
                 uint32_t *scratch, double *out) {
-  if (!nr || !T.S) return;
+  if (!nr || !T.sets.S) return;
   hipLaunchKernelGGL(sim_kernel, dim3(nr), dim3(THREADS), 0, st, T, r0, rs_off, start_base, starts, contig_len, scratch, out);
 }
 

@@ -20,14 +20,6 @@
 namespace ckm {
 using namespace simscaf;
 
-struct SimScafDev {
-  const uint32_t *nscaf;        // [G]
-  const uint32_t *sc_off;       // [G * U + 1]
-  const uint32_t *sc;
-  sim::SetsDev sets;
-  uint32_t U;
-};
-
 // replicate r0 + blockIdx.x of the call; bits holds the round's rows, the first of them being word bit_base of the call's list;
 // scratch [blocks][U] only when U > STAGE_COUNTS; out [blocks][S][4]
 __global__ __launch_bounds__(THREADS) void simscaf_kernel(SimScafDev T, uint32_t r0, const uint32_t *__restrict__ test, const uint32_t *__restrict__ cont,

@@ -23,6 +23,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "ckm_internal.h"
 #include "pairs_dev.h"
 #include "wave_const.h"
 #if defined(__HIPCC__)
@@ -62,6 +63,21 @@ struct Query {
 struct Tile { uint32_t q, ti, tj, row0; };         // query of the round, tile row and column (tj >= ti), row0 = row_off + ti * TILE
 
 MS_HD uint32_t tiles_for(uint32_t nm) { return (nm + (uint32_t)TILE - 1) / (uint32_t)TILE; }
+
+// what the kernels take by value (kernels_markerset.hip, ckm_markerset.hip)
+struct MsetTableDev {
+  const uint8_t *cls;          // [G * C]
+  const uint32_t *pos_off;     // [G * C + 1]
+  const int32_t *pos;
+  uint32_t G, C;
+};
+
+struct MsetOut {
+  const uint64_t *row_base;    // [rows of the round]: reported pairs of the rows before
+  const uint32_t *row_total;   // [rows of the round]: reported pairs of the row
+  uint64_t batch_base, cap;    // first pair of this output batch; pairs the columns hold
+  uint32_t *pi, *pj, *count;   // [cap]
+};
 
 // ---- marker pass --------------------------------------------------------------------------------------------------------------------------
 MS_HD void class_step(uint32_t c, uint32_t &ubiquity, uint32_t &single, uint32_t &duplicate) {
@@ -121,7 +137,9 @@ MS_HD uint32_t find_query(uint32_t n, uint64_t x, Key &&key) {
 }
 
 // ---- host side, shared by the library, the host executor and the stand-alone check ---------------------------------------------------------
-enum { ARGS_OK = 0, ARGS_INVALID = 1, ARGS_RANGE = 2 };
+using ckm::ARGS_INVALID;
+using ckm::ARGS_OK;
+using ckm::ARGS_RANGE;
 
 // the distance threshold as the kernels take it
 inline int check_dist(double dist_threshold, std::string &why) {

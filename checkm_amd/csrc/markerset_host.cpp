@@ -9,13 +9,10 @@ using namespace ckm;
 
 extern "C" int ckm_mset_check(uint32_t ngenomes, uint32_t nfamilies, const uint8_t *count_class, const uint64_t *pos_off, const int64_t *pos, uint32_t nqueries,
                               const uint64_t *qg_off, const uint32_t *qg, const uint64_t *qm_off, const uint32_t *qm, double dist_threshold) {
-  try {
-    std::string why;
+  return check_entry([&](std::string &why) {
     int kind = ms::check_dist(dist_threshold, why);
     if (kind == ms::ARGS_OK) kind = ms::check_table(ngenomes, nfamilies, count_class, pos_off, pos, why);
     if (kind == ms::ARGS_OK && (nqueries || qg_off)) kind = ms::check_queries(ngenomes, nfamilies, nqueries, qg_off, qg, qm_off, qm, why);
-    if (kind == ms::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == ms::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+    return kind;
+  });
 }

@@ -45,6 +45,22 @@ using pc::pair_slot;                             // where the fill pass puts a r
 
 struct PairCols { double v[NCOL]; };             // compI, contI, compJ, contJ, deltaComp, deltaCont, delta, compM, contM
 
+// what the kernels take by value (kernels_merge.hip, ckm_merge.hip)
+struct MergeBins {
+  const uint64_t *bits;        // [nbins * nwords]
+  const int64_t *hit_sum;      // [nbins]
+  const int32_t *n_markers;    // [nbins]
+  double *comp, *cont;         // [nbins]
+  uint32_t nbins, nwords;
+};
+
+struct MergeOut {
+  const uint64_t *row_base;    // [rows of the count pass]: reported pairs of the rows before
+  uint64_t batch_base, cap;    // first pair of this output batch; pairs the columns hold
+  uint32_t *pi, *pj;           // [cap]
+  double *cols;                // [NCOL * cap]
+};
+
 MG_HD int popc64(uint64_t x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __popcll(x);

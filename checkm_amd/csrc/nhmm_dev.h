@@ -27,6 +27,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "ckm_internal.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define NH_HD __host__ __device__ __forceinline__
@@ -47,7 +48,9 @@ constexpr int32_t MIN_THRESHOLD = -(1 << 20);       // no reporting threshold be
 constexpr uint32_t MAX_SPAN = 1u << 17;             // stride + overlap
 constexpr int NT = 7, NE = 4, NIMG = 12;            // transition rows, emission rows, rows of the device image (5 emission + 7 transition)
 enum { T_MM = 0, T_IM = 1, T_DM = 2, T_MI = 3, T_II = 4, T_MD = 5, T_DD = 6 };
-enum { ARGS_OK = 0, ARGS_INVALID = 1, ARGS_RANGE = 2 };
+using ckm::ARGS_INVALID;
+using ckm::ARGS_OK;
+using ckm::ARGS_RANGE;
 
 typedef long long cell;
 NH_HD cell mk(int32_t score, uint32_t start) { return (cell)(((unsigned long long)(uint32_t)score << 32) | (uint32_t)~start); }

@@ -18,13 +18,7 @@ int nhmm_check_args(const ckm_nhmm_args *a, std::string &why) {
 }  // namespace ckm
 
 extern "C" int ckm_nhmm_check(const ckm_nhmm_args *a) {
-  try {
-    std::string why;
-    const int kind = nhmm_check_args(a, why);
-    if (kind == nhmm::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == nhmm::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  return check_entry([&](std::string &why) { return nhmm_check_args(a, why); });
 }
 
 extern "C" int ckm_nhmm_columns_get(const ckm_nhmm_result *r, ckm_nhmm_columns *out) {

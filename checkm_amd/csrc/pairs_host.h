@@ -2,7 +2,6 @@
 // its totals, the split of the rows into output batches, then a fill launch and a download per batch.  Used by ckm_merge.hip and
 // ckm_markerset.hip; the buffers live as long as the call and only grow.
 #pragma once
-#include <chrono>
 #include <vector>
 #include "ckm_host.h"
 #include "pairs_dev.h"
@@ -24,20 +23,20 @@ struct PairBatches {
   template <class Scan, class Fill, class Take>
   uint64_t run(CallStream &cs, uint32_t row0, uint32_t nrows, uint64_t cap_pairs, uint64_t pair_bytes, double &ms_scan, double &ms_fill, double &ms_download, Scan &&scan, Fill &&fill,
                Take &&take) {
-    d_total.ensure((size_t)nrows * 4); d_base.ensure((size_t)nrows * 8);
+    d_total.ensure((size_t)nrows * 4);
     row_total.resize(nrows); row_base.resize(nrows);
     cs.timed(ms_scan, [&] {
       scan(d_total.as<uint32_t>());
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(row_total.data(), d_total.p, (size_t)nrows * 4, hipMemcpyDeviceToHost, cs.st));
     });
-    const auto s0 = std::chrono::steady_clock::now();
+    const WallClock s0;
     const uint64_t total = pc::row_prefix(row_total.data(), nrows, row_base.data());
     groups.clear();
     pc::plan_groups(row_total.data(), row0, row0 + nrows, cap_pairs, groups);
-    ms_scan += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s0).count();
+    ms_scan += s0.ms();
     if (!total) return 0;
-    cs.timed(ms_scan, [&] { HIPCHK(hipMemcpyAsync(d_base.p, row_base.data(), (size_t)nrows * 8, hipMemcpyHostToDevice, cs.st)); });
+    cs.timed(ms_scan, [&] { cs.put(d_base, row_base.data(), (size_t)nrows * 8); });
     for (const pc::Group &g : groups) {
       const uint64_t n = g.npairs;
       d_out.ensure(n * pair_bytes); h_out.ensure(n * pair_bytes);

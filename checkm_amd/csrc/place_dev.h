@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "ckm_internal.h"
 #include "wave_const.h"
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
@@ -247,7 +248,9 @@ struct PlaceDev {
 };
 
 // ---- host side, shared by the library, the host executor and the stand-alone check ---------------------------------------------------------
-enum { ARGS_OK = 0, ARGS_INVALID = 1, ARGS_RANGE = 2 };
+using ckm::ARGS_INVALID;
+using ckm::ARGS_OK;
+using ckm::ARGS_RANGE;
 
 struct Args {
   uint32_t nnodes; const uint64_t *child_off; const uint32_t *child; uint64_t nchild; const double *length;

@@ -21,12 +21,8 @@ int place_check_args(const ckm_place_args *a, place::Schedule &sch, std::string 
 }  // namespace ckm
 
 extern "C" int ckm_place_check(const ckm_place_args *a) {
-  try {
-    std::string why;
+  return check_entry([&](std::string &why) {
     place::Schedule sch;
-    const int kind = place_check_args(a, sch, why);
-    if (kind == place::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == place::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+    return place_check_args(a, sch, why);
+  });
 }

@@ -8,7 +8,7 @@
 //   genome_len[G]            bases of genome g; C_g = genome_len[g] / contig_len contigs (integer quotient), 1 <= C_g <= MAX_CONTIGS
 //   key_off[G * U + 1]       first key of cell (g, m) = g * U + m
 //   key[..]                  int32 start positions p[0] of the copies of marker m in genome g, each in [0, 2^31); any order
-//   ms_off / cs_off / cs_marker   the S marker sets over the U markers, exactly sim_dev.h's (check_marker_sets, mark_repeats, score_sets)
+//   ms_off / cs_off / cs_marker   the S marker sets over the U markers, marker_sets.h's two-level CSR (its check, its packing, its scores)
 //   contig_len, comp_lo, comp_hi, cont_lo, cont_hi, seed
 //
 // Generator: Philox4x32-10 (Salmon et al., SC'11) in plain 32-bit integers.  Key = (seed low half, seed high half), counter =
@@ -28,7 +28,7 @@
 //   A copy at p counts mult[p / contig_len] when p / contig_len < C, else 0 (the genome's partial tail and what lies beyond it are in
 //   no contig): what containedMarkerGenes gives for the starts c * contig_len.  A marker's count is the sum over its copies.
 //
-// Output per draw: trueComp and trueCont; four float64 per marker set (sim_dev.h's, in the reference's operation order); on request the
+// Output per draw: trueComp and trueCont; four float64 per marker set (marker_sets.h's, in the reference's operation order); on request the
 // row mult[0 .. C_g) as uint16, genome g's rows at row_off[g] = sum over h < g of R * C_h.  A row entry is min(mult, 65535): nCont <=
 // MAX_CONT_DRAWS and one completeness draw could exceed it only with every contamination draw on one contig.
 #pragma once
@@ -37,6 +37,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "marker_sets.h"
 #include "sim_dev.h"
 
 namespace ckm {
@@ -119,6 +120,18 @@ SIM_HD uint32_t marker_mult(const int32_t *key, uint32_t k0, uint32_t k1, const 
 }
 SIM_HD uint16_t row_entry(uint32_t mult) { return (uint16_t)(mult < 65535u ? mult : 65535u); }
 
+// what the kernel takes by value (kernels_select.hip, ckm_select.hip)
+struct SelectDev {
+  const int64_t *genome_len;    // [G]
+  const uint32_t *ncontigs;     // [G]
+  const uint64_t *row_off;      // [G + 1]
+  const uint32_t *key_off;      // [G * U + 1]
+  const int32_t *key;
+  msets::SetsDev sets;
+  uint32_t U, R;
+  Params P;
+};
+
 // ---- host side, shared by the library, the host executor and the stand-alone check ---------------------------------------------------------
 struct Args {
   uint32_t ngenomes; const int64_t *genome_len;
@@ -136,7 +149,7 @@ inline int check(const Args &a, uint64_t ncs, uint64_t nmembers, uint64_t nkeys,
   auto no = [&](int kind, const std::string &m) { why = m; return kind; };
   if (a.ngenomes > MAX_GENOMES) return no(ARGS_RANGE, "more than 2^24 genomes");
   if (a.nmarkers > sim::MAX_MARKERS) return no(ARGS_RANGE, "more than 2^24 markers");
-  if (a.nsets > sim::MAX_SETS) return no(ARGS_RANGE, "more than 2^20 marker sets");
+  if (a.nsets > msets::MAX_SETS) return no(ARGS_RANGE, "more than 2^20 marker sets");
   if (a.nreplicates > MAX_REPLICATES) return no(ARGS_RANGE, "more than 2^24 replicates");
   if ((uint64_t)a.ngenomes * a.nreplicates > MAX_DRAWS) return no(ARGS_RANGE, "more than 2^31 - 1 draws");
   if (!a.key_off || !a.ms_off || !a.cs_off || (a.ngenomes && !a.genome_len)) return no(ARGS_INVALID, "NULL argument");
@@ -171,12 +184,12 @@ inline int check(const Args &a, uint64_t ncs, uint64_t nmembers, uint64_t nkeys,
     if (a.key[k] < 0 || a.key[k] > 2147483647ll) return no(ARGS_RANGE, "key " + std::to_string(a.key[k]) + " does not fit int32");
   if (max_copies * ((uint64_t)max_cont + 1) > MAX_COUNT) return no(ARGS_RANGE, "copies of a marker times draws on a contig beyond 2^32 - 1");
   // marker sets
-  return sim::check_marker_sets(a.nmarkers, a.nsets, a.ms_off, a.cs_off, a.cs_marker, ncs, nmembers, why);
+  return msets::check_marker_sets(a.nmarkers, a.nsets, a.ms_off, a.cs_off, a.cs_marker, ncs, nmembers, why);
 }
 
-// The device's copies of the tables of a checked call: everything in 32 bits, the repeats marked (sim_dev.h's mark_repeats).
+// The device's copies of the tables of a checked call: everything in 32 bits.
 struct Packed {
-  sim::Packed sets;                                  // ms_off, cs_off, cs_marker, num_markers
+  msets::Packed sets;
   std::vector<uint32_t> key_off, ncontigs;           // [G * U + 1], [G]
   std::vector<int32_t> key;
   std::vector<uint64_t> row_off;                     // [G + 1]: genome g's multiplicity rows, R * C_g entries
@@ -184,12 +197,8 @@ struct Packed {
   Params params;
 };
 inline void pack(const Args &a, Packed &P) {
-  const uint64_t ncs = a.ms_off[a.nsets], nmembers = a.cs_off[ncs], cells = (uint64_t)a.ngenomes * a.nmarkers, nkeys = a.key_off[cells];
-  P.sets.ms_off.resize((size_t)a.nsets + 1); P.sets.cs_off.resize(ncs + 1); P.sets.cs_marker.resize(nmembers);
-  for (uint32_t s = 0; s <= a.nsets; ++s) P.sets.ms_off[s] = (uint32_t)a.ms_off[s];
-  for (uint64_t c = 0; c <= ncs; ++c) P.sets.cs_off[c] = (uint32_t)a.cs_off[c];
-  const sim::Args A = {a.nmarkers, nullptr, nullptr, a.nsets, a.ms_off, a.cs_off, a.cs_marker, 0, nullptr, nullptr, nullptr};
-  sim::mark_repeats(A, P.sets);
+  const uint64_t cells = (uint64_t)a.ngenomes * a.nmarkers, nkeys = a.key_off[cells];
+  msets::pack(a.nmarkers, a.nsets, a.ms_off, a.cs_off, a.cs_marker, P.sets);
   P.key_off.resize(cells + 1); P.key.resize(nkeys); P.ncontigs.resize(a.ngenomes); P.row_off.assign((size_t)a.ngenomes + 1, 0);
   for (uint64_t c = 0; c <= cells; ++c) P.key_off[c] = (uint32_t)a.key_off[c];
   for (uint64_t k = 0; k < nkeys; ++k) P.key[k] = (int32_t)a.key[k];

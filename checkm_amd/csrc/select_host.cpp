@@ -19,11 +19,5 @@ int select_check_args(const ckm_select_args *a, std::string &why) {
 }  // namespace ckm
 
 extern "C" int ckm_select_check(const ckm_select_args *a) {
-  try {
-    std::string why;
-    const int kind = select_check_args(a, why);
-    if (kind == sim::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == sim::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  return check_entry([&](std::string &why) { return select_check_args(a, why); });
 }

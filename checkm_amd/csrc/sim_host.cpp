@@ -16,11 +16,5 @@ int sim_check_args(const ckm_sim_args *a, std::string &why) {
 }  // namespace ckm
 
 extern "C" int ckm_sim_check(const ckm_sim_args *a) {
-  try {
-    std::string why;
-    const int kind = sim_check_args(a, why);
-    if (kind == sim::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == sim::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  return check_entry([&](std::string &why) { return sim_check_args(a, why); });
 }

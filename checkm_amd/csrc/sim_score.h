@@ -1,6 +1,6 @@
 // sim_score.h -- the last step of the two simulation kernels (kernels_sim.hip, kernels_simscaf.hip): MarkerSet.genomeCheck in both modes
-// (checkm/markerSets.py:206-238) for every marker set of a call, from the block's marker counts.  Device code only; the arithmetic is
-// sim_dev.h's set_terms and finish.
+// (checkm/markerSets.py:206-238) for every marker set of a call, from the block's marker counts.  Device code only; the layout and the
+// arithmetic are marker_sets.h's.
 //
 // A wavefront owns a marker set: sixty-four co-located sets at a time, a lane forms the two quotients of its set, then every lane adds the
 // sixty-four terms in list order (a broadcast read of lane l's registers), so lane 0 holds the reference's sums.  The integer sums of the
@@ -13,13 +13,6 @@
 namespace ckm {
 namespace sim {
 
-// the marker sets of a call on the device: sim_dev.h's two-level CSR in 32 bits, REPEAT marked, num_markers[s] = numMarkers() of set s
-struct SetsDev {
-  const uint32_t *ms_off;       // [S + 1]
-  const uint32_t *cs_off, *cs_marker, *num_markers;
-  uint32_t S;
-};
-
 __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 #pragma unroll
   for (int d = WAVE / 2; d > 0; d >>= 1) v += (uint64_t)__shfl_xor((unsigned long long)v, d, WAVE);
@@ -27,16 +20,16 @@ __device__ __forceinline__ uint64_t wave_sum(uint64_t v) {
 }
 
 // counts: the block's marker counts, complete and visible to every wavefront of the block; out_row [S][4], the block's own
-__device__ __forceinline__ void score_sets(const SetsDev &M, const uint32_t *counts, double *out_row) {
+__device__ __forceinline__ void score_sets(const msets::SetsDev &M, const uint32_t *counts, double *out_row) {
   const int lane = threadIdx.x & (WAVE - 1);
   for (uint32_t ms = threadIdx.x >> 6; ms < M.S; ms += WAVES) {
     const uint32_t c0 = M.ms_off[ms], c1 = M.ms_off[ms + 1];
-    Individual ind = {0u, 0ull};
+    msets::Individual ind = {0u, 0ull};
     double comp = 0.0, cont = 0.0;
     for (uint32_t base = c0; base < c1; base += WAVE) {
       const uint32_t c = base + (uint32_t)lane;
       double tc = 0.0, tn = 0.0;
-      if (c < c1) set_terms(M.cs_marker, M.cs_off[c], M.cs_off[c + 1], counts, tc, tn, ind);
+      if (c < c1) msets::set_terms(M.cs_marker, M.cs_off[c], M.cs_off[c + 1], counts, tc, tn, ind);
       const int here = c1 - base < (uint32_t)WAVE ? (int)(c1 - base) : WAVE;
       for (int l = 0; l < here; ++l) {                          // list order; the same in every lane
         comp += __shfl(tc, l, WAVE);
@@ -45,7 +38,7 @@ __device__ __forceinline__ void score_sets(const SetsDev &M, const uint32_t *cou
     }
     ind.present = (uint32_t)wave_sum(ind.present);
     ind.multi = wave_sum(ind.multi);
-    if (lane == 0) finish(ind, M.num_markers[ms], comp, cont, c1 - c0, out_row + (uint64_t)ms * 4);
+    if (lane == 0) msets::finish(ind, M.num_markers[ms], comp, cont, c1 - c0, out_row + (uint64_t)ms * 4);
   }
 }
 

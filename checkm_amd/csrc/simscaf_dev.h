@@ -2,13 +2,13 @@
 // scripts/simulationScaffoldsByLength.py of the reference, workers :137-162; MarkerSetBuilder.markerGenesOnScaffolds,
 // scripts/genometreeworkflow/markerSetBuilder.py:371-378; MarkerSet.genomeCheck, checkm/markerSets.py:206-238), written once for the kernel
 // (kernels_simscaf.hip), for the host executor of the CPU tests (tests/emu/simscaf_emu.cpp) and for the stand-alone check.  The marker
-// sets, set_terms, finish and mark_repeats are sim_dev.h's.
+// sets, their check, their packing and their scores are marker_sets.h's; the round cuts are sim_dev.h's.
 //
 // Resident, for G genomes and the U distinct markers of all marker sets of a call:
 //   nscaf[G]             scaffolds of genome g
 //   sc_off[G * U + 1]    first copy of cell (g, m) = g * U + m; sc_off[G * U] = all copies
 //   sc[..]               uint32 scaffold index < nscaf[g], one entry per copy: two copies on one scaffold are two entries
-//   ms_off, cs_off, cs_marker   the marker sets, exactly sim_dev.h's two-level CSR
+//   ms_off, cs_off, cs_marker   the marker sets, marker_sets.h's two-level CSR
 // Replicates, R of them:
 //   test[R]              the test genome, < G
 //   cont[R]              the contaminant, < G (it may be the test genome), or NONE
@@ -18,12 +18,13 @@
 //                        beyond nscaf are 0.
 //
 // A marker's count is the number of its copies in the test genome whose bit is set plus the same for the contaminant; the four float64 per
-// (replicate, marker set) follow from the counts as in sim_dev.h.
+// (replicate, marker set) follow from the counts as in marker_sets.h.
 #pragma once
 #include <algorithm>
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "marker_sets.h"
 #include "sim_dev.h"
 
 namespace ckm {
@@ -37,6 +38,8 @@ using sim::OUT_BYTES;
 using sim::ARGS_OK;
 using sim::ARGS_INVALID;
 using sim::ARGS_RANGE;
+using sim::next_round;                             // a replicate's 4-byte entries are the words of its bit rows
+using sim::replicate_bytes;
 // LDS of a block: two bit rows of 4 KiB and 16 KiB of counts = 24 KiB, six blocks (twenty-four wavefronts) on a CU's 160 KiB.
 constexpr uint32_t STAGE_BITS = 32768;              // scaffolds of a bit row staged in LDS; a longer row is read from global memory
 constexpr uint32_t STAGE_WORDS = STAGE_BITS / 32;
@@ -45,7 +48,6 @@ constexpr uint32_t MAX_GENOMES = 1u << 24;          // G
 constexpr uint32_t MAX_SCAFFOLDS = 1u << 30;        // nscaf[g]
 constexpr uint64_t MAX_CELLS = 1ull << 28;          // G * U: sc_off travels as uint32 [G * U + 1]
 constexpr uint64_t MAX_COPIES = 0x7fffffffull;      // entries of sc
-constexpr uint32_t ROUND_REPLICATES = 1u << 20;     // blocks of one launch
 
 SIM_HD uint32_t row_words(uint32_t nscaf) { return (nscaf + 31u) / 32u; }
 SIM_HD uint32_t bit_at(const uint32_t *row, uint32_t i) { return (row[i >> 5] >> (i & 31u)) & 1u; }
@@ -55,6 +57,15 @@ SIM_HD uint32_t row_count(const uint32_t *sc, uint32_t k0, uint32_t k1, const ui
   for (uint32_t k = k0; k < k1; ++k) c += bit_at(row, sc[k]);
   return c;
 }
+
+// what the kernel takes by value (kernels_simscaf.hip, ckm_simscaf.hip)
+struct SimScafDev {
+  const uint32_t *nscaf;        // [G]
+  const uint32_t *sc_off;       // [G * U + 1]
+  const uint32_t *sc;
+  msets::SetsDev sets;
+  uint32_t U;
+};
 
 // ---- host side, shared by the library, the host executor and the stand-alone check ---------------------------------------------------------
 struct Args {
@@ -91,7 +102,7 @@ inline int check(const Args &a, uint64_t nsc, uint64_t ncs, uint64_t nmembers, u
     for (uint64_t k = a.sc_off[(uint64_t)g * a.nmarkers]; k < a.sc_off[(uint64_t)(g + 1) * a.nmarkers]; ++k)
       if (a.sc[k] >= a.nscaf[g]) return no(ARGS_INVALID, "scaffold index " + std::to_string(a.sc[k]) + " beyond the scaffolds of genome " + std::to_string(g));
   // marker sets
-  if (const int kind = sim::check_marker_sets(a.nmarkers, a.nsets, a.ms_off, a.cs_off, a.cs_marker, ncs, nmembers, why)) return kind;
+  if (const int kind = msets::check_marker_sets(a.nmarkers, a.nsets, a.ms_off, a.cs_off, a.cs_marker, ncs, nmembers, why)) return kind;
   // replicates
   if (a.bit_off[0] != 0) return no(ARGS_INVALID, "bit_off does not start at 0");
   for (uint32_t r = 0; r < a.nreplicates; ++r) {
@@ -111,37 +122,16 @@ inline int check(const Args &a, uint64_t nsc, uint64_t ncs, uint64_t nmembers, u
   return ARGS_OK;
 }
 
-// The device's copies of the resident tables of a checked call: everything in 32 bits, the repeats marked.
+// The device's copies of the resident tables of a checked call: everything in 32 bits.
 struct Packed {
   std::vector<uint32_t> sc_off;
-  sim::Packed sets;                                   // ms_off, cs_off, cs_marker, num_markers
+  msets::Packed sets;
 };
 inline void pack(const Args &a, Packed &P) {
-  const uint64_t ncells = (uint64_t)a.ngenomes * a.nmarkers, ncs = a.ms_off[a.nsets], nmembers = a.cs_off[ncs];
+  const uint64_t ncells = (uint64_t)a.ngenomes * a.nmarkers;
   P.sc_off.resize(ncells + 1);
   for (uint64_t c = 0; c <= ncells; ++c) P.sc_off[c] = (uint32_t)a.sc_off[c];
-  P.sets.ms_off.resize((size_t)a.nsets + 1); P.sets.cs_off.resize(ncs + 1); P.sets.cs_marker.resize(nmembers);
-  for (uint32_t s = 0; s <= a.nsets; ++s) P.sets.ms_off[s] = (uint32_t)a.ms_off[s];
-  for (uint64_t c = 0; c <= ncs; ++c) P.sets.cs_off[c] = (uint32_t)a.cs_off[c];
-  sim::Args m = {};
-  m.nmarkers = a.nmarkers; m.nsets = a.nsets; m.ms_off = a.ms_off; m.cs_off = a.cs_off; m.cs_marker = a.cs_marker;
-  sim::mark_repeats(m, P.sets);
-}
-
-// what one replicate needs on the device during a round: its bit rows, its output rows, and a scratch row of counts when they do not fit LDS
-inline uint64_t replicate_bytes(uint64_t nwords, uint32_t nmarkers, uint32_t nsets) {
-  return nwords * 4 + (uint64_t)nsets * OUT_BYTES + (nmarkers > STAGE_COUNTS ? (uint64_t)nmarkers * 4 : 0);
-}
-// A round: replicates [r0, r1) that fit budget_bytes -- always at least one, never more than ROUND_REPLICATES.  Returns r1.
-inline uint32_t next_round(uint32_t nreplicates, const uint64_t *bit_off, uint32_t nmarkers, uint32_t nsets, uint64_t budget_bytes, uint32_t r0) {
-  uint64_t bytes = 0;
-  uint32_t r = r0;
-  for (; r < nreplicates && r - r0 < ROUND_REPLICATES; ++r) {
-    const uint64_t b = replicate_bytes(bit_off[r + 1] - bit_off[r], nmarkers, nsets);
-    if (r > r0 && bytes + b > budget_bytes) break;
-    bytes += b;
-  }
-  return r;
+  msets::pack(a.nmarkers, a.nsets, a.ms_off, a.cs_off, a.cs_marker, P.sets);
 }
 
 }  // namespace simscaf

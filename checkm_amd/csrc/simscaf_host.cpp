@@ -17,11 +17,5 @@ int simscaf_check_args(const ckm_simscaf_args *a, std::string &why) {
 }  // namespace ckm
 
 extern "C" int ckm_simscaf_check(const ckm_simscaf_args *a) {
-  try {
-    std::string why;
-    const int kind = simscaf_check_args(a, why);
-    if (kind == simscaf::ARGS_OK) return CKM_OK;
-    set_last_error(why);
-    return kind == simscaf::ARGS_RANGE ? CKM_ERANGE : CKM_EINVAL;
-  } catch (const std::bad_alloc &) { set_last_error("out of host memory"); return CKM_ENOMEM; }
+  return check_entry([&](std::string &why) { return simscaf_check_args(a, why); });
 }

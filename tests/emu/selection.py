@@ -14,7 +14,7 @@ _lib = None
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, "selection_emu.cpp"), os.path.join(_CSRC, "select_dev.h"), os.path.join(_CSRC, "sim_dev.h"), os.path.join(_HERE, "..", "..", "include", "checkm_hip.h")]
+    srcs = [os.path.join(_HERE, "selection_emu.cpp"), os.path.join(_CSRC, "select_dev.h"), os.path.join(_CSRC, "sim_dev.h"), os.path.join(_CSRC, "marker_sets.h"), os.path.join(_CSRC, "ckm_internal.h"), os.path.join(_HERE, "score_sets_emu.h"), os.path.join(_HERE, "..", "..", "include", "checkm_hip.h")]
     if force or not os.path.exists(_LIB) or any(os.path.getmtime(s) > os.path.getmtime(_LIB) for s in srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unused-function", "-Wno-unknown-pragmas", "-ffp-contract=off", "-o", _LIB,
                                os.path.join(_HERE, "selection_emu.cpp")])

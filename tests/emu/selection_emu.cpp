@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/checkm_hip.h"
 #include "../../checkm_amd/csrc/select_dev.h"
+#include "score_sets_emu.h"
 
 using namespace ckm;
 
@@ -43,28 +44,7 @@ void block(const sel::Packed &P, const int64_t *genome_len, uint32_t U, uint32_t
   const uint32_t *koff = P.key_off.data() + (uint64_t)g * U;
   for (uint32_t m = 0; m < U; ++m) counts[m] = sel::marker_mult(P.key.data(), koff[m], koff[m + 1], mult.data(), C, P.params.contig_len);
   truth.at((uint64_t)b * 2) = plan.true_comp; truth.at((uint64_t)b * 2 + 1) = plan.true_cont;
-  const sim::Packed &M = P.sets;
-  for (uint32_t wave = 0; wave < (uint32_t)sim::WAVES; ++wave)
-    for (uint32_t ms = wave; ms < S; ms += sim::WAVES) {
-      const uint32_t c0 = M.ms_off.at(ms), c1 = M.ms_off.at(ms + 1);
-      sim::Individual ind[sim::WAVE] = {};
-      double comp = 0.0, cont = 0.0;
-      for (uint32_t base = c0; base < c1; base += sim::WAVE) {
-        double tc[sim::WAVE], tn[sim::WAVE];
-        for (int lane = 0; lane < sim::WAVE; ++lane) {
-          const uint32_t c = base + (uint32_t)lane;
-          tc[lane] = tn[lane] = 0.0;
-          if (c < c1) sim::set_terms(M.cs_marker.data(), M.cs_off.at(c), M.cs_off.at(c + 1), counts, tc[lane], tn[lane], ind[lane]);
-        }
-        const int here = c1 - base < (uint32_t)sim::WAVE ? (int)(c1 - base) : sim::WAVE;
-        for (int l = 0; l < here; ++l) { comp += tc[l]; cont += tn[l]; }
-      }
-      sim::Individual all = {0u, 0ull};
-      for (int lane = 0; lane < sim::WAVE; ++lane) { all.present += ind[lane].present; all.multi += ind[lane].multi; }
-      const uint64_t at = ((uint64_t)b * S + ms) * 4;
-      (void)out.at(at + 3);
-      sim::finish(all, M.num_markers.at(ms), comp, cont, c1 - c0, &out.at(at));
-    }
+  score_sets_emu(P.sets, S, counts, b, out);
 }
 }  // namespace
 

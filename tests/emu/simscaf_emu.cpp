@@ -1,6 +1,6 @@
 // simscaf_emu.cpp -- TEST INFRASTRUCTURE: the layout, the arithmetic, the packing and the round cuts of the scaffold simulation
 // (checkm_amd/csrc/simscaf_dev.h) compiled by g++ against a HOST executor, so that the CPU test suite runs the kernel's own arithmetic.
-// simscaf_kernel of kernels_simscaf.hip and score_sets of sim_score.h are restated as loops over their blocks, wavefronts and lanes; every
+// simscaf_kernel of kernels_simscaf.hip is restated as loops over its blocks and lanes (its last step is score_sets_emu.h); every
 // buffer the kernel reads or writes has exactly the size the library gives it (the staged rows and the counts exactly the size the block
 // uses), the counts and the outputs start from poison values, so that a word that was never written shows.  Nothing in checkm_amd loads
 // this.
@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/checkm_hip.h"
 #include "../../checkm_amd/csrc/simscaf_dev.h"
+#include "score_sets_emu.h"
 
 using namespace ckm;
 
@@ -42,29 +43,7 @@ void block(const ckm_simscaf_args *a, const simscaf::Packed &P, uint32_t r0, uin
       if (h != simscaf::NONE) c += simscaf::row_count(a->sc, P.sc_off.at(ccell + m), P.sc_off.at(ccell + m + 1), crow);
       counts[m] = c;
     }
-  // score_sets
-  const sim::Packed &M = P.sets;
-  for (uint32_t wave = 0; wave < (uint32_t)sim::WAVES; ++wave)
-    for (uint32_t ms = wave; ms < S; ms += sim::WAVES) {
-      const uint32_t c0 = M.ms_off.at(ms), c1 = M.ms_off.at(ms + 1);
-      sim::Individual ind[sim::WAVE] = {};
-      double comp = 0.0, cont = 0.0;
-      for (uint32_t base = c0; base < c1; base += sim::WAVE) {
-        double tc[sim::WAVE], tn[sim::WAVE];
-        for (int lane = 0; lane < sim::WAVE; ++lane) {
-          const uint32_t c = base + (uint32_t)lane;
-          tc[lane] = tn[lane] = 0.0;
-          if (c < c1) sim::set_terms(M.cs_marker.data(), M.cs_off.at(c), M.cs_off.at(c + 1), counts, tc[lane], tn[lane], ind[lane]);
-        }
-        const int here = c1 - base < (uint32_t)sim::WAVE ? (int)(c1 - base) : sim::WAVE;
-        for (int l = 0; l < here; ++l) { comp += tc[l]; cont += tn[l]; }
-      }
-      sim::Individual all = {0u, 0ull};
-      for (int lane = 0; lane < sim::WAVE; ++lane) { all.present += ind[lane].present; all.multi += ind[lane].multi; }
-      const uint64_t at = ((uint64_t)b * S + ms) * 4;
-      (void)out.at(at + 3);
-      sim::finish(all, M.num_markers.at(ms), comp, cont, c1 - c0, &out.at(at));
-    }
+  score_sets_emu(P.sets, S, counts, b, out);
 }
 }  // namespace
 

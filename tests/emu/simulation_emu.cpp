@@ -1,14 +1,15 @@
 // simulation_emu.cpp -- TEST INFRASTRUCTURE: the layout, the arithmetic, the packing and the round cuts of the marker-set simulation
 // (checkm_amd/csrc/sim_dev.h) compiled by g++ against a HOST executor, so that the CPU test suite runs the kernel's own arithmetic.
-// sim_kernel of kernels_sim.hip is restated as loops over its blocks, wavefronts and lanes; every buffer the kernel reads or writes has
-// exactly the size the library gives it (the staged starts and the counts exactly the size the block uses), the counts and the outputs
-// start from poison values, so that a word that was never written shows.  Nothing in checkm_amd loads this.
+// sim_kernel of kernels_sim.hip is restated as loops over its blocks and lanes (its last step is score_sets_emu.h); every buffer the
+// kernel reads or writes has exactly the size the library gives it (the staged starts and the counts exactly the size the block uses),
+// the counts and the outputs start from poison values, so that a word that was never written shows.  Nothing in checkm_amd loads this.
 #include <cmath>
 #include <cstring>
 #include <limits>
 #include <vector>
 #include "../../include/checkm_hip.h"
 #include "../../checkm_amd/csrc/sim_dev.h"
+#include "score_sets_emu.h"
 
 using namespace ckm;
 
@@ -33,27 +34,7 @@ void block(const sim::Packed &P, uint32_t U, uint32_t S, uint32_t r0, uint32_t b
   const int32_t len = P.contig_len.at(r);
   for (uint32_t thread = 0; thread < (uint32_t)sim::THREADS; ++thread)
     for (uint32_t m = thread; m < U; m += sim::THREADS) counts[m] = sim::marker_count(P.key.data(), P.key_off.at(m), P.key_off.at(m + 1), s, n, len);
-  for (uint32_t wave = 0; wave < (uint32_t)sim::WAVES; ++wave)
-    for (uint32_t ms = wave; ms < S; ms += sim::WAVES) {
-      const uint32_t c0 = P.ms_off.at(ms), c1 = P.ms_off.at(ms + 1);
-      sim::Individual ind[sim::WAVE] = {};
-      double comp = 0.0, cont = 0.0;
-      for (uint32_t base = c0; base < c1; base += sim::WAVE) {
-        double tc[sim::WAVE], tn[sim::WAVE];
-        for (int lane = 0; lane < sim::WAVE; ++lane) {
-          const uint32_t c = base + (uint32_t)lane;
-          tc[lane] = tn[lane] = 0.0;
-          if (c < c1) sim::set_terms(P.cs_marker.data(), P.cs_off.at(c), P.cs_off.at(c + 1), counts, tc[lane], tn[lane], ind[lane]);
-        }
-        const int here = c1 - base < (uint32_t)sim::WAVE ? (int)(c1 - base) : sim::WAVE;
-        for (int l = 0; l < here; ++l) { comp += tc[l]; cont += tn[l]; }
-      }
-      sim::Individual all = {0u, 0ull};
-      for (int lane = 0; lane < sim::WAVE; ++lane) { all.present += ind[lane].present; all.multi += ind[lane].multi; }
-      const uint64_t at = ((uint64_t)b * S + ms) * 4;
-      (void)out.at(at + 3);
-      sim::finish(all, P.num_markers.at(ms), comp, cont, c1 - c0, &out.at(at));
-    }
+  score_sets_emu(P, S, counts, b, out);
 }
 }  // namespace
 

@@ -375,7 +375,9 @@ def test_header_and_exports_carry_the_new_names():
     makefile = open(os.path.join(ROOT, "checkm_amd", "csrc", "Makefile")).read()
     for n in ("simscaf_host.o", "kernels_simscaf.o", "ckm_simscaf.o", "simscaf_dev.h", "sim_score.h"):
         assert n in makefile
-    dev = open(os.path.join(ROOT, "checkm_amd", "csrc", "simscaf_dev.h")).read()
-    assert '#include "sim_dev.h"' in dev and "sim::mark_repeats(" in dev and "sim::check_marker_sets(" in dev
-    for restated in ("void set_terms(", "void finish(", "void mark_repeats("):       # sim_dev.h's, used and not restated
-        assert restated not in dev
+    assert "marker_sets.h" in makefile
+    for header in ("simscaf_dev.h", "select_dev.h"):
+        dev = open(os.path.join(ROOT, "checkm_amd", "csrc", header)).read()
+        assert '#include "marker_sets.h"' in dev and "msets::pack(" in dev and "msets::check_marker_sets(" in dev
+        for restated in ("void set_terms(", "void finish(", "REPEAT"):       # marker_sets.h's, used and not restated (REPEAT: the repeat marking)
+            assert restated not in dev
