@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_types.h"
+#include "queue_set.h"
+#include "pairs_wave.h"
 
 namespace ckm {
 
@@ -18,6 +20,42 @@ constexpr float LOG2E_F = 1.44269504088896341f, LN2_F = 0.69314718055994529f;
 // threadIdx alone, so it is uniform by construction and lives in scalar registers; a dynamic take with atomicAdd + readfirstlane
 // was tried first and the compiler's structurizer turned it into a loop that never left the first entry.)
 __device__ __forceinline__ uint32_t queue_len(const WorkQueue &q) { return min(*q.count, q.cap); }
+
+// A launch over a queue SET (queue_set.h): the wavefront (one per workgroup) reads the n counts once, forms the exclusive prefix of the
+// clamped lengths in LDS (pre[0 .. n]) by a wavefront scan, 64 queues at a time, and returns the total; without a set the launch's one
+// queue is the set.  The wavefronts then stride over the flat item numbers as they stride over a single queue's entries.
+__device__ __forceinline__ uint32_t queue_set_prefix(const WorkQueue &single, const QueueSet &set, uint32_t *pre, int lane) {
+  uint32_t total = 0;
+  if (set.n == 0) {
+    total = queue_len(single);
+    if (lane == 0) { pre[0] = 0; pre[1] = total; }
+  } else {
+    if (lane == 0) pre[0] = 0;
+    for (uint32_t base = 0; base < set.n; base += WAVE) {
+      const uint32_t i = base + (uint32_t)lane;
+      uint32_t v = 0;
+      if (i < set.n) { const WorkQueue q = set.queues[i]; v = qs_clamp(*q.count, q.cap); }
+      const uint32_t incl = wave_inclusive(v, lane);
+      if (i < set.n) pre[i + 1] = total + incl;
+      total += __shfl(incl, WAVE - 1, WAVE);
+    }
+  }
+  __syncthreads();
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)total);
+}
+
+// Flat item k of the launch: its queue's index in the set and its entry.  Every lane computes the same values from LDS; they are handed
+// on through readfirstlane so that the item, like an entry taken by blockIdx alone, lives in scalar registers.
+__device__ __forceinline__ uint32_t queue_set_item(const WorkQueue &single, const QueueSet &set, const uint32_t *pre, uint32_t k, uint32_t &qi) {
+  if (set.n == 0) { qi = 0; return single.list[k]; }
+  uint32_t q = 0, pos = 0;
+  qs_locate(pre, set.n, k, q, pos);
+  q = (uint32_t)__builtin_amdgcn_readfirstlane((int)q); pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)pos);
+  qi = q;
+  // (the list pointer comes out of memory, so the entry is fetched by a flat load into a vector register: back to a scalar one, or the
+  //  work item's record and everything derived from it -- lengths, offsets, the model -- would live in vector registers for the whole pass)
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)set.queues[q].list[pos]);
+}
 
 // natural logarithm for the conservative tests only (v_log_f32, ~1 ulp in log2)
 __device__ __forceinline__ float approx_ln(float x) { return __log2f(x) * LN2_F; }

@@ -359,6 +359,31 @@ inline CascadePlan cascade_plan(uint64_t prof_uid, uint64_t seq_uid, const SeqRa
   return pl;
 }
 
+// ---- the float stages' queue sets (queue_set.h) ---------------------------------------------------------------------------------
+// The float stages run once per FLUSH and Forward class: a flush is where the trace ensembles of a sequence part are launched, behind
+// the filter chains of all of the part's groups (parts beyond the third share the last flush, as they share its ensemble queue).  A
+// set's members are the groups of the flush whose models reach the class, in launch order; sets come in flush order, and inside a
+// flush the class with the most registers first (its launches last longest).
+inline int flush_slot(int part) { return std::min(part, 3); }
+struct FloatSet { int slot, cls; uint32_t first, n; };           // members[first .. first + n)
+struct FloatSets { std::vector<FloatSet> sets; std::vector<uint32_t> members; };
+inline FloatSets float_sets(const PlanGroups &groups, const std::vector<Sub> &subs, const std::vector<size_t> &order) {
+  FloatSets fs;
+  size_t a = 0;
+  while (a < order.size()) {
+    const int slot = flush_slot(group_part(groups[order[a]].first));
+    size_t b = a;
+    while (b < order.size() && flush_slot(group_part(groups[order[b]].first)) == slot) ++b;
+    for (int c = NFC - 1; c >= 0; --c) {
+      const uint32_t first = (uint32_t)fs.members.size();
+      for (size_t k = a; k < b; ++k) if (subs[order[k]].fb[c]) fs.members.push_back((uint32_t)order[k]);
+      if (fs.members.size() > first) fs.sets.push_back({slot, c, first, (uint32_t)fs.members.size() - first});
+    }
+    a = b;
+  }
+  return fs;
+}
+
 // ---- what a drained search teaches ----------------------------------------------------------------------------------------------
 struct Overflow { const char *what; int group, cls; uint64_t wanted, cap; };      // a table that was too small: (group, class) -1 where there is none
 struct Lesson {

@@ -105,6 +105,7 @@ extern "C" int ckm_ctx_create(int device, ckm_ctx **out) {
       for (auto &e : w.cls_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
       for (auto &e : w.grp_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
       for (auto &e : w.ens_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&w.set_ev, hipEventDisableTiming));
       memset(&w.stats, 0, sizeof(w.stats));
       w.ws_budget = budget;
       // the float workspace is an address reservation with 1 GB chunks mapped in as it grows (DevBuf::grow_mapped): find() reserves the
@@ -149,6 +150,7 @@ extern "C" void ckm_ctx_destroy(ckm_ctx *ctx) {
     for (auto &e : w.cls_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : w.grp_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : w.ens_ev) if (e) (void)hipEventDestroy(e);
+    if (w.set_ev) (void)hipEventDestroy(w.set_ev);
     if (w.late[0]) (void)hipStreamDestroy(w.late[0]);
     if (!w.own_streams) continue;                      // (handles of the device's pool: they live as long as the process)
     for (int k = 0; k < w.nside; ++k) (void)hipStreamDestroy(w.side[k]);

@@ -26,6 +26,7 @@
 #include "marker_sets.h"
 #include "stream_plan.h"
 #include "cascade_plan.h"
+#include "queue_set.h"
 
 namespace ckm {
 
@@ -46,19 +47,20 @@ int launch_vit(int QH, uint32_t nblocks, hipStream_t stream, WorkQueue queue, co
                uint32_t *out_flag, bool fast, const CascadeDev *cd /* null: scores only */);
 int launch_fwd(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, FbWork *work, const DevModel *models,
                const LenEntry *lentab, const uint8_t *res, const uint64_t *seq_off, float *ws, FwdOut *out,
-               ScaleEvent *events, uint32_t *nevents, uint32_t cap_events, const CascadeDev *cd /* null: no F3 epilogue */);
+               ScaleEvent *events, uint32_t *nevents, uint32_t cap_events, const QueueSet *set = nullptr /* the launch runs over a queue set (queue_set.h), not over `queue` */,
+               const CascadeDev *cds = nullptr /* device array, one per group of the set's search: the F3 epilogue runs; null: none */);
 int launch_bwd(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, const FbWork *work, const DevModel *models,
-               const LenEntry *lentab, const uint8_t *res, const uint64_t *seq_off, float *ws, const FwdOut *fout, int32_t *range_err);
+               const LenEntry *lentab, const uint8_t *res, const uint64_t *seq_off, float *ws, const FwdOut *fout, int32_t *range_err, const QueueSet *set = nullptr);
 int launch_oa(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, const FbWork *work, const DevModel *models,
-              float *ws, const int32_t *range_err, const FwdOut *fout, EnvOut *out);
+              float *ws, const int32_t *range_err, const FwdOut *fout, EnvOut *out, const QueueSet *set = nullptr);
 
 void launch_ensemble(hipStream_t stream, const EnsWork *work, const uint32_t *list /* indices into work, or null */, const uint32_t *count, uint32_t cap, uint32_t grid_regions, int max_Mp,
                      const DevModel *models, const LenEntry *lentab, const uint8_t *res, const uint64_t *seq_off, float *ws, const uint32_t *seeds,
                      float *host_res /* pinned buffer the results are exported to, or null */);
 void launch_bias_filter(hipStream_t stream, uint32_t nblocks, const CascadeDev &cd, const DevModel *models, const LenEntry *lentab,
                         const uint8_t *res, const uint64_t *seq_off);
-void launch_regions(hipStream_t stream, uint32_t nblocks, const uint32_t *list, const uint32_t *count, uint32_t cap, const FbWork *fwork,
-                    const CascadeDev &cd, const DevModel *models, float *ws);
+int launch_regions(hipStream_t stream, uint32_t nblocks, const QueueSet &set /* Backward queues of the parser items */, const FbWork *fwork,
+                   const CascadeDev *cds /* device array, one per group */, const DevModel *models, float *ws);
 #define HIPCHK(expr)                                                                                         \
   do {                                                                                                       \
     hipError_t e_ = (expr);                                                                                  \
@@ -315,6 +317,8 @@ struct Worker {
   hipStream_t late[4] = {};                                      // high-priority streams of the short rounds that follow a search's drain (run_fb with late_round set)
   bool late_round = false;
   hipEvent_t grp_ev[192] = {};                                    // end of the SSV launch of each model-length group
+  DevBuf c_setq, c_setg, c_cds;                                  // the float stages' queue sets (queue_set.h) and every group's CascadeDev, uploaded once per search
+  hipEvent_t set_ev = nullptr;                                   // ... that upload -> the lane's launches
 };
 
 // register classes of the Viterbi-filter and Forward/Backward kernels, in queue order (DevModel::vit_cls / fb_cls index these)

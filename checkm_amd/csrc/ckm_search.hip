@@ -570,6 +570,45 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   uint32_t *h_cnt = pin_table<uint32_t>(ctx->h_cnt, (NG + 1) * CC_SIZE);
   ensure_ens_seeds(ctx);
   float *ws = ctx->ws.as<float>();
+  // ---- every group's tables (its SSV launch and its filter chain take them by value) and the queue sets of the float stages: per flush
+  // and Forward class the fq / bq / eq / rq queues of the flush's groups (cascade_plan.h: float_sets).  Both go to the device once, staged;
+  // the lane's launches wait for the copy by an event, the host does not ----
+  auto ens_slot = [](int part) { return flush_slot(part); };
+  std::vector<CascadeDev> cds(NG, cd0);
+  for (size_t g = 0; g < NG; ++g) {
+    const Sub &sb = subs[g]; CascadeDev &cd = cds[g];
+    const int sl = ens_slot(group_part(groups[g].first));
+    cd.cnt = d_gcnt + (1 + g) * CC_SIZE;
+    cd.cand = d_cand + sb.o_cand; cd.cap_cand = sb.cap_cand;
+    cd.bias_raw = d_bias + 2 * sb.o_cand; cd.vit_fast = d_vfast + sb.o_cand; cd.vit_exact = d_vexact + sb.o_cand; cd.vit_flag = d_vflag + sb.o_cand; cd.route = d_route + sb.o_cand;
+    cd.vq = d_vq + sb.o_vq; cd.vxq = d_vxq + sb.o_vq; cd.cap_vq = sb.cap_cand;
+    cd.fq = d_fq + sb.o_f; cd.bq = d_bq + sb.o_f; cd.cap_fq = sb.cap_f;
+    cd.eq = d_eq + sb.o_e; cd.cap_eq = sb.cap_e;
+    cd.rq = d_rq + sb.o_r; cd.cap_rq = sb.cap_r;
+    cd.ensq = d_ensq + (size_t)sl * cp.rwork; cd.ensq_cnt = d_gcnt + CC_ENSQ + sl;
+  }
+  static_assert(kMaxGroups <= QS_MAX, "a queue set holds a queue of every group");
+  const FloatSets fsets = float_sets(groups, subs, plan.order);
+  const size_t NM = fsets.members.size();
+  enum { SQ_F = 0, SQ_B, SQ_E, SQ_R, SQ_N };            // a member's four queues: stage s of member k is entry s * NM + k
+  const WorkQueue *d_setq = dev_table<WorkQueue>(ctx->c_setq, SQ_N * NM);
+  const uint32_t *d_setg = dev_table<uint32_t>(ctx->c_setg, NM);
+  const CascadeDev *d_cds = dev_table<CascadeDev>(ctx->c_cds, NG);
+  {
+    std::vector<WorkQueue> hq(SQ_N * NM);
+    for (const FloatSet &fs : fsets.sets)
+      for (uint32_t k = fs.first; k < fs.first + fs.n; ++k) {
+        const CascadeDev &cd = cds[fsets.members[k]]; const size_t c = (size_t)fs.cls;
+        hq[SQ_F * NM + k] = WorkQueue{cd.fq + c * cd.cap_fq, cd.cnt + CC_FQ + c, cd.cap_fq};
+        hq[SQ_B * NM + k] = WorkQueue{cd.bq + c * cd.cap_fq, cd.cnt + CC_BQ + c, cd.cap_fq};
+        hq[SQ_E * NM + k] = WorkQueue{cd.eq + c * cd.cap_eq, cd.cnt + CC_EQ + c, cd.cap_eq};
+        hq[SQ_R * NM + k] = WorkQueue{cd.rq + c * cd.cap_rq, cd.cnt + CC_RQ + c, cd.cap_rq};
+      }
+    ctx->stager.begin(hq.size() * sizeof(WorkQueue) + NM * sizeof(uint32_t) + NG * sizeof(CascadeDev));
+    if (NM) { ctx->stager.put(ctx->late[2], ctx->c_setq.p, hq.data(), hq.size() * sizeof(WorkQueue)); ctx->stager.put(ctx->late[2], ctx->c_setg.p, fsets.members.data(), NM * sizeof(uint32_t)); }
+    ctx->stager.put(ctx->late[2], ctx->c_cds.p, cds.data(), NG * sizeof(CascadeDev));
+    HIPCHK(hipEventRecord(ctx->set_ev, ctx->late[2]));
+  }
   CKM_TRACE_PT("tables ready");
   const int NS = ctx->nside;
   const int NSS = ctx->nss;                        // streams of the SSV launches (stream_plan.h, by the hardware queues the process runs with)
@@ -588,6 +627,7 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
   const int stop = getenv("CKM_CHAIN_STOP") ? atoi(getenv("CKM_CHAIN_STOP")) : 99;
   HIPCHK(hipMemsetAsync(d_gcnt, 0, (NG + 1) * CC_SIZE * sizeof(uint32_t), ms));
   HIPCHK(hipMemsetAsync(d_tops, 0, 4 * sizeof(unsigned long long), ms));
+  HIPCHK(hipStreamWaitEvent(ms, ctx->set_ev, 0));            // the queue sets and the groups' tables are on the device
   if (owner->ssv_prev_done) HIPCHK(hipStreamWaitEvent(ms, owner->ssv_prev_done, 0));     // previous lane's SSV launches
   // ... and the SSV launches of whichever search was queued on this DEVICE before this one, another context's included (find() keeps two
   // contexts in flight): two SSV phases side by side finish together, the two host threads then do their between-searches work at the
@@ -616,12 +656,39 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
     for (const Sub &sb : subs) for (int c = 0; c < NFC; ++c) if (sb.fb[c]) ens_Mp = std::max(ens_Mp, kFbQ[c] * NL);
     hipStream_t es = ctx->ens_stream;
     bool ens_launched = false;
-    auto ens_slot = [](int part) { return std::min(part, 3); };
+    // The float stages of a flush: parser Forward, Backward, regions, envelope Forward / Backward / OA, region Forward -- ONE launch per stage
+    // and Forward class over the queue sets of all of the flush's groups, behind the filter chains of every one of them (each chain handle
+    // marks its end, the class's handle waits for the others).  The classes do not depend on one another: they go round the chain
+    // handles, the class with the most registers first, and the trace ensembles wait for all of them.  Per group, as it was until round 25,
+    // every stage of every group lasted as long as the group's longest sequence, once per SSV class of the part for the same few long
+    // sequences.
     auto flush_part = [&](int part) {
-      if (stop < 13) return;
+      if (stop < 6) return;
       const int k0 = NCH > 0 ? NSS : 0, k1 = NCH > 0 ? NS : NSS;
-      for (int k = k0; k < k1; ++k) { HIPCHK(hipEventRecord(ctx->ens_ev[k], ctx->side[k])); HIPCHK(hipStreamWaitEvent(es, ctx->ens_ev[k], 0)); }
       const int sl = ens_slot(part);
+      for (int k = k0; k < k1; ++k) HIPCHK(hipEventRecord(ctx->ens_ev[k], ctx->side[k]));
+      int rc = 0, at = 0;
+      for (const FloatSet &fs : fsets.sets) if (fs.slot == sl) {
+        const int h = k0 + at++ % (k1 - k0);
+        hipStream_t sc = ctx->side[h];
+        for (int k = k0; k < k1; ++k) if (k != h) HIPCHK(hipStreamWaitEvent(sc, ctx->ens_ev[k], 0));
+        const int Q = kFbQ[fs.cls];
+        const QueueSet qf{d_setq + SQ_F * NM + fs.first, d_setg + fs.first, fs.n}, qb{d_setq + SQ_B * NM + fs.first, d_setg + fs.first, fs.n};
+        const QueueSet qe{d_setq + SQ_E * NM + fs.first, d_setg + fs.first, fs.n}, qr{d_setq + SQ_R * NM + fs.first, d_setg + fs.first, fs.n};
+        const WorkQueue none{nullptr, nullptr, 0};
+        // one launch per stage (a fused Forward -> F3 -> Backward -> regions kernel was measured in round 2: same rows, 2-3 % slower -- it
+        // holds 1.5-2x the registers and the launch boundaries it removes are hidden underneath the SSV launches -- and removed in round 3)
+        if (stop >= 6) rc |= launch_fwd(Q, GRID_FB, sc, none, cd0.fwork, dm, lt, res, off, ws, d_fout_f, d_events_f, d_gcnt + CC_EVENTS, cp.events_f, &qf, d_cds);
+        if (stop >= 7) rc |= launch_bwd(Q, GRID_FB, sc, none, cd0.fwork, dm, lt, res, off, ws, d_fout_f, nullptr, &qb);
+        if (stop >= 8) rc |= launch_regions(sc, 1024, qb, cd0.fwork, d_cds, dm, ws);
+        if (stop >= 9) rc |= launch_fwd(Q, GRID_FB, sc, none, cd0.ework, dm, lt, res, off, ws, d_fout_e, d_events_e, d_gcnt + CC_EVENTS_E, cp.events_e, &qe, nullptr);
+        if (stop >= 10) rc |= launch_bwd(Q, GRID_FB, sc, none, cd0.ework, dm, lt, res, off, ws, d_fout_e, d_rerr_e, &qe);
+        if (stop >= 11) rc |= launch_oa(Q, GRID_FB, sc, none, cd0.ework, dm, ws, d_rerr_e, d_fout_e, d_envout, &qe);
+        if (stop >= 12) rc |= launch_fwd(Q, std::max(64u, GRID_FB / 8), sc, none, cd0.rwork, dm, lt, res, off, ws, d_fout_r, d_events_r, d_gcnt + CC_EVENTS_R, 1 << 16, &qr, nullptr);
+      }
+      if (rc) throw Error(CKM_ERANGE, "no kernel instance for this model length");
+      if (stop < 13) return;
+      for (int k = k0; k < k1; ++k) { HIPCHK(hipEventRecord(ctx->ens_ev[k], ctx->side[k])); HIPCHK(hipStreamWaitEvent(es, ctx->ens_ev[k], 0)); }
       launch_ensemble(es, cd0.ens, d_ensq + (size_t)sl * cp.rwork, d_gcnt + CC_ENSQ + sl, cp.rwork, 64, ens_Mp, dm, lt, res, off, ws, ctx->ensseeds.as<uint32_t>(), d_hens);
       ens_launched = true;
     };
@@ -634,16 +701,8 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
       cur_part = part;
       hipStream_t sv = ctx->side[gi_now % NSS];
       // ---- the group's tables; its SSV launch appends survivors (-> candidate table) and undecided pairs (-> exact-MSV table) itself ----
-      CascadeDev cd = cd0;
-      uint32_t *cnt = d_gcnt + (1 + g) * CC_SIZE;
-      cd.cnt = cnt;
-      cd.cand = d_cand + sb.o_cand; cd.cap_cand = sb.cap_cand;
-      cd.bias_raw = d_bias + 2 * sb.o_cand; cd.vit_fast = d_vfast + sb.o_cand; cd.vit_exact = d_vexact + sb.o_cand; cd.vit_flag = d_vflag + sb.o_cand; cd.route = d_route + sb.o_cand;
-      cd.vq = d_vq + sb.o_vq; cd.vxq = d_vxq + sb.o_vq; cd.cap_vq = sb.cap_cand;
-      cd.fq = d_fq + sb.o_f; cd.bq = d_bq + sb.o_f; cd.cap_fq = sb.cap_f;
-      cd.eq = d_eq + sb.o_e; cd.cap_eq = sb.cap_e;
-      cd.rq = d_rq + sb.o_r; cd.cap_rq = sb.cap_r;
-      cd.ensq = d_ensq + (size_t)ens_slot(part) * cp.rwork; cd.ensq_cnt = d_gcnt + CC_ENSQ + ens_slot(part);
+      const CascadeDev &cd = cds[g];
+      uint32_t *cnt = cd.cnt;
       PairRec *nores = d_nores + sb.o_nores;
       const SsvEpi epi{lt, cd.cand, cnt + CC_CAND, sb.cap_cand, nores, cnt + CC_NORES, sb.cap_nores, nullptr};
       if (launch_ssv(sb.Q, (int)sb.nblocks, ssv_threads_for(sb.Q), sv, ctx->work.as<SsvBlockWork>() + sb.first, dm, res, off, dlen,
@@ -671,20 +730,6 @@ static int cascade_dev(Worker *ctx, ckm_ctx *owner, int my_turn, const ckm_profi
       }
       for (int c = NVC - 1; c >= NV16; --c) if (sb.vit[c] && stop >= 5)
         rc |= launch_vit(kVitQH[c - NV16], std::max(64u, GRID_VIT / 4), sc, WorkQueue{cd.vxq + (size_t)c * cd.cap_vq, cnt + CC_VXQ + c, cd.cap_vq}, cd.cand, dm, lt, res, off, dlen, nullptr, nullptr, nullptr, false, &cd);
-      for (int c = NFC - 1; c >= 0; --c) if (sb.fb[c]) {
-        const int Q = kFbQ[c];
-        const WorkQueue qf{cd.fq + (size_t)c * sb.cap_f, cnt + CC_FQ + c, sb.cap_f}, qb{cd.bq + (size_t)c * sb.cap_f, cnt + CC_BQ + c, sb.cap_f};
-        const WorkQueue qe{cd.eq + (size_t)c * sb.cap_e, cnt + CC_EQ + c, sb.cap_e}, qr{cd.rq + (size_t)c * sb.cap_r, cnt + CC_RQ + c, sb.cap_r};
-        // one launch per stage (a fused Forward -> F3 -> Backward -> regions kernel was measured in round 2: same rows, 2-3 % slower -- it
-        // holds 1.5-2x the registers and the launch boundaries it removes are hidden underneath the SSV launches -- and removed in round 3)
-        if (stop >= 6) rc |= launch_fwd(Q, GRID_FB, sc, qf, cd.fwork, dm, lt, res, off, ws, d_fout_f, d_events_f, d_gcnt + CC_EVENTS, cp.events_f, &cd);
-        if (stop >= 7) rc |= launch_bwd(Q, GRID_FB, sc, qb, cd.fwork, dm, lt, res, off, ws, d_fout_f, nullptr);
-        if (stop >= 8) launch_regions(sc, 1024, qb.list, qb.count, sb.cap_f, cd.fwork, cd, dm, ws);
-        if (stop >= 9) rc |= launch_fwd(Q, GRID_FB, sc, qe, cd.ework, dm, lt, res, off, ws, d_fout_e, d_events_e, d_gcnt + CC_EVENTS_E, cp.events_e, nullptr);
-        if (stop >= 10) rc |= launch_bwd(Q, GRID_FB, sc, qe, cd.ework, dm, lt, res, off, ws, d_fout_e, d_rerr_e);
-        if (stop >= 11) rc |= launch_oa(Q, GRID_FB, sc, qe, cd.ework, dm, ws, d_rerr_e, d_fout_e, d_envout);
-        if (stop >= 12) rc |= launch_fwd(Q, std::max(64u, GRID_FB / 8), sc, qr, cd.rwork, dm, lt, res, off, ws, d_fout_r, d_events_r, d_gcnt + CC_EVENTS_R, 1 << 16, nullptr);
-      }
       if (rc) throw Error(CKM_ERANGE, "no kernel instance for this model length");
     }
     if (cur_part >= 0) flush_part(cur_part);

@@ -155,7 +155,8 @@ struct RegionRec {                    // one region found by the posterior heuri
   uint32_t pad;                       // multi: float offset of the region's exported ensemble results in the pinned buffer (0xffffffff: none)
 };
 
-struct CascadeDev {                   // by-value kernel argument: where the epilogues of the filter / Forward / Backward kernels put their output
+struct CascadeDev {                   // where the epilogues of the filter / Forward / Backward kernels put their output: one per group, a by-value kernel
+                                      // argument of the group's filter chain and an entry of the device array the float stages' queue sets index (queue_set.h)
   PairRec *cand; uint32_t cap_cand;
   float *bias_raw;                    // [cap_cand][2]
   float *vit_fast, *vit_exact; uint32_t *vit_flag; uint8_t *route;      // [cap_cand]

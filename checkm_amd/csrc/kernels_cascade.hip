@@ -17,21 +17,26 @@ namespace ckm {
 
 
 
-// list/count: a queue of parser items of `fwork` whose decoding terms are complete (the host-visible form of the stage; the cascade
-// itself runs the scan inside the fused parser kernel)
-__global__ void __launch_bounds__(64) region_kernel(const uint32_t *__restrict__ list, const uint32_t *__restrict__ count, uint32_t cap,
-                                                   const FbWork *__restrict__ fwork, CascadeDev cd, const DevModel *__restrict__ models, float *__restrict__ ws) {
-  const uint32_t n = min(*count, cap);
+// set: the Backward queues (parser items of `fwork` whose decoding terms are complete) of one register class over all groups of a
+// sequence part (queue_set.h); cds: the search's CascadeDev array.  What a region becomes goes to the tables, queues and counters of the
+// group its pair came from.
+__global__ void __launch_bounds__(64) region_kernel(QueueSet set, const FbWork *__restrict__ fwork, const CascadeDev *__restrict__ cds,
+                                                   const DevModel *__restrict__ models, float *__restrict__ ws) {
+  __shared__ uint32_t qpre[QS_MAX + 1];
   const int lane = threadIdx.x;
+  const uint32_t n = queue_set_prefix(WorkQueue{nullptr, nullptr, 0}, set, qpre, lane);
   for (uint32_t k = blockIdx.x; k < n; k += gridDim.x) {
-    const FbWork w = fwork[list[k]];
-    region_scan<false>(cd, models[w.model], w, ws, lane);
+    uint32_t qi;
+    const uint32_t item = queue_set_item(WorkQueue{nullptr, nullptr, 0}, set, qpre, k, qi);
+    const FbWork w = fwork[item];
+    region_scan<false>(cds[set.group[qi]], models[w.model], w, ws, lane);
   }
 }
 
-void launch_regions(hipStream_t stream, uint32_t nblocks, const uint32_t *list, const uint32_t *count, uint32_t cap, const FbWork *fwork,
-                    const CascadeDev &cd, const DevModel *models, float *ws) {
-  if (nblocks) hipLaunchKernelGGL(region_kernel, dim3(nblocks), dim3(64), 0, stream, list, count, cap, fwork, cd, models, ws);
+int launch_regions(hipStream_t stream, uint32_t nblocks, const QueueSet &set, const FbWork *fwork, const CascadeDev *cds, const DevModel *models, float *ws) {
+  if (!set.n || set.n > QS_MAX || !cds) return -1;
+  if (nblocks) hipLaunchKernelGGL(region_kernel, dim3(nblocks), dim3(64), 0, stream, set, fwork, cds, models, ws);
+  return 0;
 }
 
 }  // namespace ckm

@@ -9,7 +9,6 @@
 // Reference stage replaced: Forward/Backward/domain definition of the hmmsearch per-target pipeline
 // (process launched at checkm/hmmer.py:70).
 #include <hip/hip_runtime.h>
-#include <cstring>
 #include "dev_types.h"
 #include "cascade_dev.h"
 #include "cascade_regions.h"
@@ -43,8 +42,12 @@ struct Tr {
 
 // A workgroup is ONE wavefront that takes work items from a queue (dev_types.h: WorkQueue) until the queue is empty: the queue
 // may have been written by the host (alignment requests, diagnostics, second envelope rounds) or by the kernels of the previous
-// stage (the device-driven cascade, ckm_cascade.hip), in which case its length is only known on the device.  The wavefront
-// keeps the transition image of its current model in LDS and reloads it when the model changes.
+// stage (the device-driven cascade, ckm_search.hip), in which case its length is only known on the device.  The device-driven
+// cascade launches a stage ONCE per sequence part and register class over a queue SET (queue_set.h, cascade_dev.h): the queues of
+// that stage and class of all of the part's groups, taken as one flat list -- the wavefront forms the prefix of their lengths in
+// LDS, finds the queue of each of its flat item numbers by binary search, and where an epilogue hands the item on (Forward's F3
+// decision) it does so into the tables, queues and counters of the group the queue belongs to.  The wavefront keeps the transition
+// image of its current model in LDS and reloads it when the model changes.
 template <int Q>
 __device__ __forceinline__ void load_tr(float *lds, const float *ftr) {
   constexpr int Mp = Q * 64;
@@ -188,49 +191,56 @@ __device__ __forceinline__ void fwd_item(const FbWork &w, const DevModel &md, fl
   o_xC = xC; o_nscale = nscale; o_lsum = lsum; o_move = move;
 }
 
+// The F3 decision of a whole-sequence parser item of the device-driven cascade, taken conservatively by lane 0 (the threshold is lowered
+// by a margin that covers the approximate logarithms; the host repeats the test exactly).  A passer gets its pass record, the workspace
+// of its decoding terms, and a place in the Backward queue of this register class -- the queue and the counters of the item's OWN group.
+__device__ __forceinline__ void fwd_decide(const CascadeDev &cd, const DevModel &md, const FbWork &w, FbWork *__restrict__ work, uint32_t item,
+                                           float xC, int nscale, float lsum, float move) {
+  const PairRec pr = cd.cand[w.cand];
+  const float fwdsc = lsum + approx_ln(xC * move);
+  const float sc = (fwdsc - pr.filtersc) * LOG2E_F;
+  if (sc >= md.thr_fwd_f3 - cd.margin_fwd) {
+    unsigned long long off;
+    if (ws_alloc(cd, (unsigned long long)(w.Ld + 1) * 3ull, off)) {
+      const uint32_t pid = atomicAdd(&cd.gcnt[CC_PASS], 1u);
+      if (pid < cd.cap_pass) {
+        PassRec r;
+        r.cand = w.cand; r.fwork = item; r.model = w.model; r.seq = w.seq; r.usc = pr.usc;
+        r.bias_d = cd.bias_raw[2 * (size_t)w.cand]; r.bias_e = cd.bias_raw[2 * (size_t)w.cand + 1];
+        r.vit_fast = cd.vit_fast[w.cand]; r.vit_exact = cd.vit_exact[w.cand]; r.vit_flag = cd.vit_flag[w.cand]; r.route = cd.route[w.cand];
+        r.fwd_xC = xC; r.nscale = nscale;
+        cd.h_pass[pid] = r;
+        work[item].aux_off = off; work[item].pass = pid;
+        queue_push(cd, cd.bq, CC_BQ, md.fb_cls, cd.cap_fq, item, (uint32_t)CS_FWORK);
+      } else atomicOr(&cd.gcnt[CC_STATUS], (uint32_t)CS_PASS);
+    }
+  }
+}
+
+// queue / set: the launch's one queue, or (set.n > 0) a queue set (queue_set.h) -- the queues of one stage and register class over all
+// groups of a sequence part.  cds: null, or the search's CascadeDev array (one per group): the F3 epilogue runs, for the item's group.
 template <int Q>
-__global__ void __launch_bounds__(64) fwd_kernel(WorkQueue queue, FbWork *__restrict__ work,
+__global__ void __launch_bounds__(64) fwd_kernel(WorkQueue queue, QueueSet set, FbWork *__restrict__ work,
                                                 const DevModel *__restrict__ models, const LenEntry *__restrict__ lentab,
                                                 const uint8_t *__restrict__ res, const uint64_t *__restrict__ seq_off,
                                                 float *__restrict__ ws, FwdOut *__restrict__ out,
                                                 ScaleEvent *__restrict__ events, uint32_t *__restrict__ nevents, uint32_t cap_events,
-                                                CascadeDev cd, int decide) {
+                                                const CascadeDev *__restrict__ cds) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  __shared__ uint32_t qpre[QS_MAX + 1];
   const int lane = threadIdx.x;
   uint32_t cur_model = 0xffffffffu;
- const uint32_t nqueue = queue_len(queue);
+ const uint32_t nqueue = queue_set_prefix(queue, set, qpre, lane);
  for (uint32_t qk = blockIdx.x; qk < nqueue; qk += gridDim.x) {
-  const uint32_t item = queue.list[qk];
+  uint32_t qi;
+  const uint32_t item = queue_set_item(queue, set, qpre, qk, qi);
   const FbWork w = work[item];
   const DevModel &md = models[w.model];
   if (w.model != cur_model) { load_tr<Q>(lds, md.ftr); cur_model = w.model; }
   float xC, lsum, move; int nscale;
   fwd_item<Q>(w, md, lds, lane, lentab, res, seq_off, ws, events, nevents, cap_events, xC, nscale, lsum, move);
   if (lane == 0) { out[w.slot].xC = xC; out[w.slot].nscale = nscale; }
-  // ---- device-driven cascade: the F3 decision of a whole-sequence parser item, taken conservatively (the threshold is lowered by a
-  // margin that covers the approximate logarithms; the host repeats the test exactly).  A passer gets its pass record, the workspace
-  // of its decoding terms, and a place in the Backward queue of this register class.
-  if (decide && lane == 0) {
-    const PairRec pr = cd.cand[w.cand];
-    const float fwdsc = lsum + approx_ln(xC * move);
-    const float sc = (fwdsc - pr.filtersc) * LOG2E_F;
-    if (sc >= md.thr_fwd_f3 - cd.margin_fwd) {
-      unsigned long long off;
-      if (ws_alloc(cd, (unsigned long long)(w.Ld + 1) * 3ull, off)) {
-        const uint32_t pid = atomicAdd(&cd.gcnt[CC_PASS], 1u);
-        if (pid < cd.cap_pass) {
-          PassRec r;
-          r.cand = w.cand; r.fwork = item; r.model = w.model; r.seq = w.seq; r.usc = pr.usc;
-          r.bias_d = cd.bias_raw[2 * (size_t)w.cand]; r.bias_e = cd.bias_raw[2 * (size_t)w.cand + 1];
-          r.vit_fast = cd.vit_fast[w.cand]; r.vit_exact = cd.vit_exact[w.cand]; r.vit_flag = cd.vit_flag[w.cand]; r.route = cd.route[w.cand];
-          r.fwd_xC = xC; r.nscale = nscale;
-          cd.h_pass[pid] = r;
-          work[item].aux_off = off; work[item].pass = pid;
-          queue_push(cd, cd.bq, CC_BQ, md.fb_cls, cd.cap_fq, item, (uint32_t)CS_FWORK);
-        } else atomicOr(&cd.gcnt[CC_STATUS], (uint32_t)CS_PASS);
-      }
-    }
-  }
+  if (cds && lane == 0) fwd_decide(cds[set.n ? set.group[qi] : 0u], md, w, work, item, xC, nscale, lsum, move);
  }
 }
 
@@ -418,16 +428,18 @@ __device__ __forceinline__ void bwd_item(const FbWork &w, const DevModel &md, fl
 }
 
 template <int Q>
-__global__ void __launch_bounds__(64) bwd_kernel(WorkQueue queue, const FbWork *__restrict__ work,
+__global__ void __launch_bounds__(64) bwd_kernel(WorkQueue queue, QueueSet set, const FbWork *__restrict__ work,
                                                 const DevModel *__restrict__ models, const LenEntry *__restrict__ lentab,
                                                 const uint8_t *__restrict__ res, const uint64_t *__restrict__ seq_off,
                                                 float *__restrict__ ws, const FwdOut *__restrict__ fout, int32_t *__restrict__ range_err) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  __shared__ uint32_t qpre[QS_MAX + 1];
   const int lane = threadIdx.x;
   uint32_t cur_model = 0xffffffffu;
- const uint32_t nqueue = queue_len(queue);
+ const uint32_t nqueue = queue_set_prefix(queue, set, qpre, lane);
  for (uint32_t qk = blockIdx.x; qk < nqueue; qk += gridDim.x) {
-  const uint32_t item = queue.list[qk];
+  uint32_t qi;
+  const uint32_t item = queue_set_item(queue, set, qpre, qk, qi);
   const FbWork w = work[item];
   const DevModel &md = models[w.model];
   if (w.model != cur_model) { load_tr<Q>(lds, md.ftr); cur_model = w.model; }
@@ -619,15 +631,17 @@ __device__ __forceinline__ void oa_item(const FbWork &w, const DevModel &md, flo
 }
 
 template <int Q>
-__global__ void __launch_bounds__(64) oa_kernel(WorkQueue queue, const FbWork *__restrict__ work,
+__global__ void __launch_bounds__(64) oa_kernel(WorkQueue queue, QueueSet set, const FbWork *__restrict__ work,
                                                const DevModel *__restrict__ models, float *__restrict__ ws,
                                                const int32_t *__restrict__ range_err, const FwdOut *__restrict__ fout, EnvOut *__restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
+  __shared__ uint32_t qpre[QS_MAX + 1];
   const int lane = threadIdx.x;
   uint32_t cur_model = 0xffffffffu;
- const uint32_t nqueue = queue_len(queue);
+ const uint32_t nqueue = queue_set_prefix(queue, set, qpre, lane);
  for (uint32_t qk = blockIdx.x; qk < nqueue; qk += gridDim.x) {
-  const uint32_t item = queue.list[qk];
+  uint32_t qi;
+  const uint32_t item = queue_set_item(queue, set, qpre, qk, qi);
   const FbWork w = work[item];
   const DevModel &md = models[w.model];
   if (w.model != cur_model) { load_gates<Q>(lds, md.ftr); cur_model = w.model; }
@@ -645,14 +659,16 @@ static void allow_big_lds(K kernel, int Q) {
   if (Q >= 48) (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * Q * 64 * 4);
 }
 
+// set: null, or the queue set the launch runs over in place of `queue` (set->n queues, at most QS_MAX).  cds: null, or the search's
+// CascadeDev array on the device: the F3 epilogue runs for every item, into the tables of the group its queue belongs to.
 int launch_fwd(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, FbWork *work, const DevModel *models,
                const LenEntry *lentab, const uint8_t *res, const uint64_t *seq_off, float *ws, FwdOut *out,
-               ScaleEvent *events, uint32_t *nevents, uint32_t cap_events, const CascadeDev *cd) {
+               ScaleEvent *events, uint32_t *nevents, uint32_t cap_events, const QueueSet *set, const CascadeDev *cds) {
   if (!nblocks) return 0;
-  CascadeDev c; memset(&c, 0, sizeof(c));
-  if (cd) c = *cd;
+  const QueueSet qs = set ? *set : QueueSet{nullptr, nullptr, 0};
+  if (qs.n > QS_MAX || (cds && !qs.n)) return -1;
   switch (Q) {
-#define X(QV) case QV: allow_big_lds(fwd_kernel<QV>, QV); hipLaunchKernelGGL(fwd_kernel<QV>, dim3(nblocks), dim3(64), (size_t)8 * QV * 64 * 4, stream, queue, work, models, lentab, res, seq_off, ws, out, events, nevents, cap_events, c, cd ? 1 : 0); break;
+#define X(QV) case QV: allow_big_lds(fwd_kernel<QV>, QV); hipLaunchKernelGGL(fwd_kernel<QV>, dim3(nblocks), dim3(64), (size_t)8 * QV * 64 * 4, stream, queue, qs, work, models, lentab, res, seq_off, ws, out, events, nevents, cap_events, cds); break;
     CKM_FB_QS(X)
 #undef X
     default: return -1;
@@ -660,10 +676,12 @@ int launch_fwd(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, FbW
   return 0;
 }
 int launch_bwd(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, const FbWork *work, const DevModel *models,
-               const LenEntry *lentab, const uint8_t *res, const uint64_t *seq_off, float *ws, const FwdOut *fout, int32_t *range_err) {
+               const LenEntry *lentab, const uint8_t *res, const uint64_t *seq_off, float *ws, const FwdOut *fout, int32_t *range_err, const QueueSet *set) {
   if (!nblocks) return 0;
+  const QueueSet qs = set ? *set : QueueSet{nullptr, nullptr, 0};
+  if (qs.n > QS_MAX) return -1;
   switch (Q) {
-#define X(QV) case QV: allow_big_lds(bwd_kernel<QV>, QV); hipLaunchKernelGGL(bwd_kernel<QV>, dim3(nblocks), dim3(64), (size_t)8 * QV * 64 * 4, stream, queue, work, models, lentab, res, seq_off, ws, fout, range_err); break;
+#define X(QV) case QV: allow_big_lds(bwd_kernel<QV>, QV); hipLaunchKernelGGL(bwd_kernel<QV>, dim3(nblocks), dim3(64), (size_t)8 * QV * 64 * 4, stream, queue, qs, work, models, lentab, res, seq_off, ws, fout, range_err); break;
     CKM_FB_QS(X)
 #undef X
     default: return -1;
@@ -671,10 +689,12 @@ int launch_bwd(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, con
   return 0;
 }
 int launch_oa(int Q, uint32_t nblocks, hipStream_t stream, WorkQueue queue, const FbWork *work, const DevModel *models,
-              float *ws, const int32_t *range_err, const FwdOut *fout, EnvOut *out) {
+              float *ws, const int32_t *range_err, const FwdOut *fout, EnvOut *out, const QueueSet *set) {
   if (!nblocks) return 0;
+  const QueueSet qs = set ? *set : QueueSet{nullptr, nullptr, 0};
+  if (qs.n > QS_MAX) return -1;
   switch (Q) {
-#define X(QV) case QV: allow_big_lds(oa_kernel<QV>, QV); hipLaunchKernelGGL(oa_kernel<QV>, dim3(nblocks), dim3(64), (size_t)8 * QV * 64 * 4, stream, queue, work, models, ws, range_err, fout, out); break;
+#define X(QV) case QV: allow_big_lds(oa_kernel<QV>, QV); hipLaunchKernelGGL(oa_kernel<QV>, dim3(nblocks), dim3(64), (size_t)8 * QV * 64 * 4, stream, queue, qs, work, models, ws, range_err, fout, out); break;
     CKM_FB_QS(X)
 #undef X
     default: return -1;

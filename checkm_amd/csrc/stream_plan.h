@@ -3,13 +3,16 @@
 // it alone.
 //
 // A context has 1 main stream (fork / join of a search, uploads), up to 14 side streams -- the first `nss` carry the SSV launches, the
-// next `nch` the groups' chains -- and 1 stream for the trace ensembles.  Streams that share a hardware queue run one behind the other,
+// next `nch` the chains: every group's filter chain (exact MSV, bias filter, Viterbi) behind its SSV launch, and once per sequence part
+// and Forward class the float stages over the queue sets of all of the part's groups (queue_set.h), the classes going round the same
+// handles -- and 1 stream for the trace ensembles.  Streams that share a hardware queue run one behind the other,
 // and a hipStreamWaitEvent barrier holds everything queued behind it on its queue: with more streams than queues an SSV launch sits
 // behind a chain that waits for ANOTHER SSV launch, and the device runs under-filled through the SSV phase.  So
 // the pool never holds more streams than the budget, and below 16 queues
 //   - an SSV handle carries SSV launches only: no chain, no ensemble, no main stream (they wait on other streams' events and run
 //     persistent queue kernels);
-//   - the chains of all groups, and of all contexts, share the chain handles in launch order -- their SSV launches finish in that order;
+//   - the filter chains of all groups, and of all contexts, share the chain handles in launch order -- their SSV launches finish in that
+//     order; a part's float stages queue on them behind the part's last filter chain, in front of the next part's;
 //   - up to 4 queues every handle but the one SSV handle is a chain handle, and the main stream and the ensembles use the last of them:
 //     the chain kernels are latency-bound and their serial time exceeds the SSV launches', so what counts is how many run side by
 //     side (measured at 4 queues, s per 1000-bin step: SSV 1 + chain 3: 12.5; 1 + 2 + a main: 13.1; 2 + 2: 13.2; 1 + 1 + two mains:
