@@ -276,6 +276,22 @@ class GtreeInfo(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("nrounds", "ntrees", "launches")] + [(f, C.c_double) for f in _GTREE_MS]
 
 
+class GenetreeArgs(C.Structure):
+    _fields_ = [("ntrees", C.c_uint32)] + [(f, C.c_void_p) for f in ("node_off", "leaf_off", "class_off", "group_off", "gpair_off", "first", "last", "parent", "length", "internal",
+                                                                     "leaf_genome", "leaf_species", "leaf_class", "class_total", "pair_a", "pair_b")]
+
+
+class GenetreeOut(C.Structure):
+    _fields_ = [(f, C.c_void_p) for f in ("consistency", "pair_flag", "group_node", "group_mixed")]
+
+
+_GENETREE_MS = ("ms_upload", "ms_consistency", "ms_flags", "ms_conspecific", "ms_download", "ms_total")
+
+
+class GenetreeInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("nrounds", "ntrees", "launches")] + [(f, C.c_double) for f in _GENETREE_MS]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -316,6 +332,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
            "ckm_sim_check", "ckm_sim_run", "ckm_simscaf_check", "ckm_simscaf_run", "ckm_select_check", "ckm_select_run", "ckm_place_check", "ckm_place_run",
            "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free", "ckm_gtree_check", "ckm_gtree_host", "ckm_gtree_run",
+           "ckm_genetree_check", "ckm_genetree_host", "ckm_genetree_run",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_envelope_paths", "ckm_debug_region"]
 
 _lib = None
@@ -464,6 +481,9 @@ def load():
     L.ckm_gtree_check.argtypes = [C.POINTER(GtreeArgs)]
     L.ckm_gtree_host.argtypes = [C.POINTER(GtreeArgs), C.c_uint64, C.POINTER(GtreeOut), C.POINTER(GtreeInfo)]
     L.ckm_gtree_run.argtypes = [C.c_void_p, C.POINTER(GtreeArgs), C.c_uint64, C.POINTER(GtreeOut), C.POINTER(GtreeInfo)]
+    L.ckm_genetree_check.argtypes = [C.POINTER(GenetreeArgs)]
+    L.ckm_genetree_host.argtypes = [C.POINTER(GenetreeArgs), C.c_uint64, C.POINTER(GenetreeOut), C.POINTER(GenetreeInfo)]
+    L.ckm_genetree_run.argtypes = [C.c_void_p, C.POINTER(GenetreeArgs), C.c_uint64, C.POINTER(GenetreeOut), C.POINTER(GenetreeInfo)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -1962,3 +1982,58 @@ def gtree_host(tables, budget_bytes=0, counts=False, dist=False, merges=True):
     """The same call through the host executor (ckm_gtree_host): the same bits, no device.  For checks and comparisons; nothing in the
     package calls it in place of the device."""
     return _gtree_call(load().ckm_gtree_host, tables, budget_bytes, counts, dist, merges)
+
+
+GENETREE_MAX_LEAVES, GENETREE_MAX_NODES, GENETREE_MAX_CLASSES = 1 << 14, 1 << 15, 65535
+GENETREE_NONE = 0xffffffff
+_GENETREE_FIELDS = (("node_off", np.uint32), ("leaf_off", np.uint32), ("class_off", np.uint32), ("group_off", np.uint32), ("gpair_off", np.uint32), ("first", np.uint32),
+                    ("last", np.uint32), ("parent", np.uint32), ("length", np.float64), ("internal", np.uint8), ("leaf_genome", np.uint32), ("leaf_species", np.uint32),
+                    ("leaf_class", np.uint32), ("class_total", np.uint32), ("pair_a", np.uint32), ("pair_b", np.uint32))
+
+
+class GenetreeTables(object):
+    """The packed forest of one gene-tree call as ckm_genetree_check / ckm_genetree_run take it (include/checkm_hip.h): node_off, leaf_off,
+    group_off [ntrees + 1], class_off [3 ntrees + 1], gpair_off [groups + 1]; first, last, parent (uint32), length (float64), internal
+    (uint8) per node; leaf_genome, leaf_species per leaf and leaf_class [3, leaves]; class_total per class; pair_a, pair_b per pair."""
+
+    def __init__(self, ntrees, **arrays):
+        self.ntrees = int(ntrees)
+        for f, dt in _GENETREE_FIELDS:
+            setattr(self, f, np.ascontiguousarray(arrays[f], dtype=dt).reshape(-1))
+        self.nclasses, self.npairs, self.ngroups = int(self.class_off[-1]), int(self.gpair_off[-1]), int(self.group_off[-1])
+
+    def args(self):
+        """The ckm_genetree_args of these arrays (it borrows them: keep this object alive over the call)."""
+        return GenetreeArgs(self.ntrees, *[getattr(self, f).ctypes.data if getattr(self, f).size else None for f, _ in _GENETREE_FIELDS])
+
+
+def genetree_check(tables):
+    """ckm_genetree_check: why the forest of a call would be refused, without a device.  Raises CkmError as genetree_run would."""
+    a = tables.args()
+    _chk(load().ckm_genetree_check(C.byref(a)))
+
+
+def _genetree_call(entry, tables, budget_bytes):
+    a = tables.args()
+    _chk(load().ckm_genetree_check(C.byref(a)))               # (the output shapes below need offsets that are in order)
+    o = dict(consistency=np.zeros(tables.nclasses), pair_flag=np.zeros(tables.npairs, dtype=np.uint8), group_node=np.zeros(tables.ngroups, dtype=np.uint32),
+             group_mixed=np.zeros(tables.ngroups, dtype=np.uint8))
+    info = GenetreeInfo()
+    go = GenetreeOut(*[o[f].ctypes.data if o[f].size else None for f in ("consistency", "pair_flag", "group_node", "group_mixed")])
+    _chk(entry(C.byref(a), int(budget_bytes), C.byref(go), C.byref(info)))
+    o.update({f: int(getattr(info, f)) for f in ("nrounds", "ntrees", "launches")})
+    o.update({f: getattr(info, f) for f in _GENETREE_MS})
+    return o
+
+
+def genetree_run(ctx, tables, budget_bytes=0):
+    """The gene-tree tests of a packed forest (ckm_genetree_run).  Returns a dict: consistency [classes] float64, pair_flag [pairs] uint8,
+    group_node [groups] uint32 (GENETREE_NONE: no flagged pair), group_mixed [groups] uint8; nrounds, ntrees, launches and the timings in ms."""
+    L = load()
+    return _genetree_call(lambda a, b, o, i: L.ckm_genetree_run(ctx.h, a, b, o, i), tables, budget_bytes)
+
+
+def genetree_host(tables, budget_bytes=0):
+    """The same call through the host executor (ckm_genetree_host): the same bits, no device.  For checks and comparisons; nothing in the
+    package calls it in place of the device."""
+    return _genetree_call(load().ckm_genetree_host, tables, budget_bytes)

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_*, ckm_nhmm_*, ckm_select_* and ckm_gtree_* */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_*, ckm_nhmm_*, ckm_select_*, ckm_gtree_* and ckm_genetree_* */
 
 enum {
   CKM_OK      =  0,
@@ -982,6 +982,49 @@ typedef struct {
 int  ckm_gtree_check(const ckm_gtree_args *a);
 int  ckm_gtree_host(const ckm_gtree_args *a, uint64_t budget_bytes, const ckm_gtree_out *out, ckm_gtree_info *info);
 int  ckm_gtree_run(ckm_ctx *ctx, const ckm_gtree_args *a, uint64_t budget_bytes, const ckm_gtree_out *out, ckm_gtree_info *info);
+
+/* ---- GeneTrees: the paralog and consistency tests of a forest of gene trees (additions to ABI 12) ---------------------------
+ * Replaces the dendropy walks of scripts/genometreeworkflow/paralogTest.py and consistencyTest.py by integer problems over leaf ranges
+ * (checkm_amd/csrc/genetree_dev.h states layout and arithmetic), on the device in kernels_genetree.hip.
+ *
+ * Forest: ntrees trees; the leaves of a tree are numbered in the order they are written.  Tree t has the nodes node_off[t] ..
+ * node_off[t+1] in pre-order as written (node 0 the root): first, last (its subtree is the leaf range [first, last) of the tree), parent
+ * (a node of the tree, 0xffffffff for the root), length (float64, the root's 0 when absent), internal (1: it has children); the leaves
+ * leaf_off[t] .. leaf_off[t+1]: leaf_genome and leaf_species (dense per tree; species 0xffffffff: not counted) and leaf_class, rank-major
+ * over all leaves of the call (leaf_class[r * nleaves + leaf]; r = 0 domain, 1 phylum, 2 class), dense per tree and rank; the classes
+ * class_off[3t+r] .. class_off[3t+r+1] of rank r with class_total, the class's leaves in the tree; the groups group_off[t] ..
+ * group_off[t+1], one per genome with several leaves, group g holding the leaf pairs gpair_off[g] .. gpair_off[g+1] (pair_a < pair_b,
+ * positions in the tree).
+ *
+ * Outputs: consistency [classes] float64, the maximum over the internal nodes of k / (T + (n - k)) and (T - k) / (T + ((N - n) - (T - k)))
+ * (one IEEE division each, start value 0); pair_flag [pairs], 1 when the patristic distance of the pair is > 0 (summed up the first side
+ * to the common ancestor, the second side added onto it; two root distances, each summed from the leaf up, when the ancestor is the
+ * root); group_node [groups], the node of the smallest subtree over every flagged leaf of the group (0xffffffff: no flagged pair), and
+ * group_mixed [groups], 1 when the counted species in that subtree take more than one value.  Trees are processed in rounds of at most
+ * budget_bytes (0: CKM_GENETREE_BATCH_MB, default 256) of resident arrays; no result depends on the budget.
+ *
+ * Refused, nothing computed: CKM_ERANGE for more than 2^14 leaves or 2^15 nodes in a tree, more than 65535 classes at a rank, more than
+ * 2^20 trees; CKM_EINVAL for a NULL argument, offsets that descend, an empty tree, a length that is not finite, a leaf range outside the
+ * tree, a parent that does not precede its child, children that do not tile their parent's range, a class index beyond the class count,
+ * a class total that is not the count of its leaves, a pair that names a leaf beyond the tree, is not ascending or joins two genomes.
+ * ckm_genetree_check applies the same tests and needs no device.  ckm_genetree_host is the host executor of genetree_dev.h behind the
+ * same arguments: the same bits as ckm_genetree_run, no device (the times of its info stay 0). */
+typedef struct {
+  uint32_t ntrees;
+  const uint32_t *node_off, *leaf_off, *class_off, *group_off, *gpair_off;
+  const uint32_t *first, *last, *parent;   const double *length;   const uint8_t *internal;
+  const uint32_t *leaf_genome, *leaf_species, *leaf_class;
+  const uint32_t *class_total;
+  const uint32_t *pair_a, *pair_b;
+} ckm_genetree_args;
+typedef struct { double *consistency;   uint8_t *pair_flag;   uint32_t *group_node;   uint8_t *group_mixed; } ckm_genetree_out;
+typedef struct {
+  uint64_t nrounds, ntrees, launches;
+  double   ms_upload, ms_consistency, ms_flags, ms_conspecific, ms_download, ms_total;
+} ckm_genetree_info;
+int  ckm_genetree_check(const ckm_genetree_args *a);
+int  ckm_genetree_host(const ckm_genetree_args *a, uint64_t budget_bytes, const ckm_genetree_out *out, ckm_genetree_info *info);
+int  ckm_genetree_run(ckm_ctx *ctx, const ckm_genetree_args *a, uint64_t budget_bytes, const ckm_genetree_out *out, ckm_genetree_info *info);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
