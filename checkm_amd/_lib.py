@@ -292,6 +292,21 @@ class GenetreeInfo(C.Structure):
     _fields_ = [(f, C.c_uint64) for f in ("nrounds", "ntrees", "launches")] + [(f, C.c_double) for f in _GENETREE_MS]
 
 
+class NearidArgs(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("n_rows", C.c_uint32), ("row_len", C.c_uint32), ("row_stride", C.c_uint32), ("limit", C.c_void_p)]
+
+
+class NearidOut(C.Structure):
+    _fields_ = [("near", C.c_void_p)]
+
+
+_NEARID_MS = ("ms_upload", "ms_kernel", "ms_download", "ms_total")
+
+
+class NearidInfo(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("nbands", "npairs", "launches", "blocks")] + [(f, C.c_double) for f in _NEARID_MS]
+
+
 class GeneColumns(C.Structure):
     _fields_ = [("n", C.c_uint64), ("bin", C.POINTER(C.c_uint32)), ("contig", C.POINTER(C.c_uint32)), ("begin", C.POINTER(C.c_int32)), ("end", C.POINTER(C.c_int32)),
                 ("strand", C.POINTER(C.c_int8)), ("start_type", C.POINTER(C.c_uint8)), ("partial_left", C.POINTER(C.c_uint8)), ("partial_right", C.POINTER(C.c_uint8)),
@@ -332,7 +347,7 @@ EXPORTS = ["ckm_last_error", "ckm_abi_version", "ckm_device_count", "ckm_ctx_cre
            "ckm_mset_check", "ckm_mset_table_create", "ckm_mset_table_free", "ckm_mset_markers", "ckm_mset_colocated", "ckm_mset_columns_get", "ckm_mset_result_free",
            "ckm_sim_check", "ckm_sim_run", "ckm_simscaf_check", "ckm_simscaf_run", "ckm_select_check", "ckm_select_run", "ckm_place_check", "ckm_place_run",
            "ckm_nhmm_check", "ckm_nhmm_run", "ckm_nhmm_columns_get", "ckm_nhmm_free", "ckm_gtree_check", "ckm_gtree_host", "ckm_gtree_run",
-           "ckm_genetree_check", "ckm_genetree_host", "ckm_genetree_run",
+           "ckm_genetree_check", "ckm_genetree_host", "ckm_genetree_run", "ckm_nearid_check", "ckm_nearid_host", "ckm_nearid_run",
            "ckm_debug_stages", "ckm_debug_ssv", "ckm_debug_filters", "ckm_debug_envelopes", "ckm_debug_envelope_paths", "ckm_debug_region"]
 
 _lib = None
@@ -484,6 +499,9 @@ def load():
     L.ckm_genetree_check.argtypes = [C.POINTER(GenetreeArgs)]
     L.ckm_genetree_host.argtypes = [C.POINTER(GenetreeArgs), C.c_uint64, C.POINTER(GenetreeOut), C.POINTER(GenetreeInfo)]
     L.ckm_genetree_run.argtypes = [C.c_void_p, C.POINTER(GenetreeArgs), C.c_uint64, C.POINTER(GenetreeOut), C.POINTER(GenetreeInfo)]
+    L.ckm_nearid_check.argtypes = [C.POINTER(NearidArgs)]
+    L.ckm_nearid_host.argtypes = [C.POINTER(NearidArgs), C.c_uint64, C.POINTER(NearidOut), C.POINTER(NearidInfo)]
+    L.ckm_nearid_run.argtypes = [C.c_void_p, C.POINTER(NearidArgs), C.c_uint64, C.POINTER(NearidOut), C.POINTER(NearidInfo)]
     L.ckm_debug_orf_flags.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     L.ckm_debug_stages.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
     L.ckm_debug_ssv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
@@ -2037,3 +2055,64 @@ def genetree_host(tables, budget_bytes=0):
     """The same call through the host executor (ckm_genetree_host): the same bits, no device.  For checks and comparisons; nothing in the
     package calls it in place of the device."""
     return _genetree_call(load().ckm_genetree_host, tables, budget_bytes)
+
+
+NEARID_MAX_ROWS, NEARID_MAX_STRIDE, NEARID_MAX_TEXT_BYTES = 1 << 17, 1 << 24, 1 << 34
+
+
+class NearidTables(object):
+    """The arrays of one near-identity call as ckm_nearid_check / ckm_nearid_run take them (include/checkm_hip.h).  rows: a list of equally
+    long bytes objects, or a [n_rows, row_len] uint8 array; they are copied into one uint8 array [n_rows, row_stride] whose stride is
+    row_len rounded up to a multiple of 16, padded with 0.  limit: per row i, the pairs (i, j > i) are near iff they differ in fewer
+    columns."""
+
+    def __init__(self, rows, limit):
+        if isinstance(rows, np.ndarray):
+            body = np.ascontiguousarray(rows, dtype=np.uint8)
+            body = body.reshape(body.shape[0], -1)
+        else:
+            rows = list(rows)
+            body = np.frombuffer(b"".join(rows), dtype=np.uint8).reshape(len(rows), len(rows[0]) if rows else 0)
+        self.n_rows, self.row_len = int(body.shape[0]), int(body.shape[1])
+        self.row_stride = max(16, (self.row_len + 15) // 16 * 16)
+        self.text = np.zeros((self.n_rows, self.row_stride), dtype=np.uint8)
+        self.text[:, :self.row_len] = body
+        self.limit = np.ascontiguousarray(limit, dtype=np.uint32).reshape(-1)
+        if self.limit.shape[0] != self.n_rows:
+            raise ValueError("one limit per row")
+        self.words = (self.n_rows + 63) // 64
+
+    def args(self):
+        """The ckm_nearid_args of these arrays (it borrows them: keep this object alive over the call)."""
+        return NearidArgs(self.text.ctypes.data if self.text.size else None, self.n_rows, self.row_len, self.row_stride, self.limit.ctypes.data if self.limit.size else None)
+
+
+def nearid_check(tables):
+    """ckm_nearid_check: why a call would be refused, without a device.  Raises CkmError as nearid_run would."""
+    a = tables.args()
+    _chk(load().ckm_nearid_check(C.byref(a)))
+
+
+def _nearid_call(entry, tables, budget_bytes):
+    a = tables.args()
+    _chk(load().ckm_nearid_check(C.byref(a)))                 # (the output shape below needs a call that is in range)
+    o = dict(near=np.zeros((tables.n_rows, tables.words), dtype=np.uint64))
+    info = NearidInfo()
+    no = NearidOut(o["near"].ctypes.data)
+    _chk(entry(C.byref(a), int(budget_bytes), C.byref(no), C.byref(info)))
+    o.update({f: int(getattr(info, f)) for f in ("nbands", "npairs", "launches", "blocks")})
+    o.update({f: getattr(info, f) for f in _NEARID_MS})
+    return o
+
+
+def nearid_run(ctx, tables, budget_bytes=0):
+    """The near-identity pass (ckm_nearid_run).  Returns a dict: near [n_rows, ceil(n_rows / 64)] uint64, bit (j & 63) of word j // 64 of row
+    i set iff j > i and rows i and j differ in fewer than limit[i] columns; nbands, npairs, launches, blocks and the timings in ms."""
+    L = load()
+    return _nearid_call(lambda a, b, o, i: L.ckm_nearid_run(ctx.h, a, b, o, i), tables, budget_bytes)
+
+
+def nearid_host(tables, budget_bytes=0):
+    """The same call through the host executor (ckm_nearid_host): the same bits, no device.  For checks and comparisons; nothing in the
+    package calls it in place of the device."""
+    return _nearid_call(load().ckm_nearid_host, tables, budget_bytes)

@@ -411,6 +411,27 @@ class GenomeTree(object):
         fresh = parse_newick(_newick(new_root))                   # numbered as written
         return _newick(fresh) if as_text else fresh
 
+    # ---- seqmagick --deduplicate-sequences -----------------------------------------------------------------------------------------------
+    @staticmethod
+    def deduplicate(alignFile, derepAlignFile, derepSeqFile):
+        """Rows of alignFile with identical text collapse onto the first id in file order: derepAlignFile keeps the first occurrences in
+        file order, derepSeqFile gets one line `kept dup1 dup2 ...` per kept id that has duplicates (what MarkerSetBuilder.readDuplicateSeqs
+        and DecorateTree read).  A host dict; no kernel.  Returns {kept id: [duplicates]} for the ids that have any."""
+        seqs = readFasta(alignFile)
+        first, dups = {}, {}
+        with open(derepAlignFile, 'w') as fout:
+            for seqId, seq in seqs.items():
+                if seq not in first:
+                    first[seq] = seqId
+                    fout.write('>' + seqId + '\n')
+                    fout.write(seq + '\n')
+                else:
+                    dups.setdefault(first[seq], []).append(seqId)
+        with open(derepSeqFile, 'w') as fout:
+            for kept, others in dups.items():
+                fout.write(' '.join([kept] + others) + '\n')
+        return dups
+
     # ---- the reference's entry --------------------------------------------------------------------------------------------------------
     def run(self, geneTreeDir, alignmentDir, extension, outputAlignFile, outputTree, outputTaxonomy, bSupportValues=False, img=None, numBootstraps=100, model='kimura',
             maxDist=3.0):

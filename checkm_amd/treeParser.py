@@ -150,6 +150,34 @@ class Tree(object):
         return self._leaf.get(taxon)
 
 
+def _quote(name):
+    if name and all(ch.isalnum() or ch in '_.-|' for ch in name):
+        return name
+    return "'" + name.replace("'", "''") + "'"
+
+
+def write_newick(tree, labels=True):
+    """The tree as one Newick statement read_newick reads back: leaves by taxon, internal nodes by label (labels=False: none), lengths
+    as repr(float); names with other characters than letters, digits and _.-| are quoted.  Iterative: a tree may be a comb."""
+    out, stack = [], [(tree.root, 0)]
+    while stack:
+        v, k = stack.pop()
+        if v.children and k < len(v.children):
+            out.append('(' if k == 0 else ',')
+            stack.append((v, k + 1))
+            stack.append((v.children[k], 0))
+            continue
+        if v.children:
+            out.append(')')
+            if labels and v.label:
+                out.append(_quote(v.label))
+        else:
+            out.append(_quote(v.taxon if v.taxon is not None else ''))
+        if v.parent is not None and v.length is not None:
+            out.append(':' + repr(float(v.length)))
+    return ''.join(out) + ';'
+
+
 _PY2_SET = re.compile(r'set\(\[(.*?)\]\)', re.S)
 
 

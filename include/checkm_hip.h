@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_*, ckm_nhmm_*, ckm_select_*, ckm_gtree_* and ckm_genetree_* */
+#define CKM_ABI_VERSION 12   /* the MarkerSetBuilder entries (ckm_mset_*) are additive: CKM_ABI_VERSION stays 12; so are ckm_sim_*, ckm_simscaf_*, ckm_place_*, ckm_nhmm_*, ckm_select_*, ckm_gtree_*, ckm_genetree_* and ckm_nearid_* */
 
 enum {
   CKM_OK      =  0,
@@ -1025,6 +1025,33 @@ typedef struct {
 int  ckm_genetree_check(const ckm_genetree_args *a);
 int  ckm_genetree_host(const ckm_genetree_args *a, uint64_t budget_bytes, const ckm_genetree_out *out, ckm_genetree_info *info);
 int  ckm_genetree_run(ckm_ctx *ctx, const ckm_genetree_args *a, uint64_t budget_bytes, const ckm_genetree_out *out, ckm_genetree_info *info);
+
+/* ---- ReducedTree: which pairs of rows of an alignment are nearly identical (additions to ABI 12) ----------------------------
+ * Replaces the all-pairs Python loop of scripts/genometreeworkflow/createSmallTree.py (__nearlyIdentical) by one pass over the upper
+ * triangle (checkm_amd/csrc/nearid_dev.h states layout and arithmetic), on the device in kernels_nearid.hip.
+ *
+ * Text: n_rows rows of row_len raw bytes, row i at text + i * row_stride; row_stride >= row_len and a multiple of 16.  The bytes between
+ * row_len and row_stride are never compared.  Every byte value counts as itself, gaps and 0x80 .. 0xFF included.  A pair (i, j > i) is
+ * near iff the number of columns at which the two rows differ is below limit[i] (>= 1; the caller computes it with the reference's own
+ * float expression, the library sees integers only).
+ * Output: near [n_rows][ceil(n_rows / 64)] uint64, bit (j & 63) of word j / 64 of row i set iff j > i and the pair is near; every word
+ * is written.  The text and the limits stay resident; the row tiles (64 rows) are cut into bands whose bit rows fit what budget_bytes
+ * (0: CKM_NEARID_BATCH_MB, default 256, << 20) leaves beside them, never fewer than one row tile; no result depends on the budget.
+ *
+ * Refused, nothing computed: CKM_EINVAL for a NULL argument, n_rows == 0, row_len == 0, a limit of 0, a row_stride below row_len or not
+ * a multiple of 16; CKM_ERANGE for more than 2^17 rows (the bit matrix stays at or below 2 GiB), a row_stride above 2^24, more than
+ * 2^34 bytes of text (n_rows * row_stride).  ckm_nearid_check applies the same tests and needs no device.  ckm_nearid_host is the host
+ * executor of nearid_dev.h behind the same arguments: the same bits as ckm_nearid_run, no device (the times of its info stay 0). */
+typedef struct { const uint8_t *text; uint32_t n_rows, row_len, row_stride;   /* rows padded to a multiple of 16 */
+                 const uint32_t *limit; } ckm_nearid_args;                   /* per row i: pairs (i, j > i) are near iff diffs < limit[i] */
+typedef struct { uint64_t *near; } ckm_nearid_out;                            /* [n_rows][ceil(n_rows/64)] bit j of row i, only j > i set */
+typedef struct {
+  uint64_t nbands, npairs, launches, blocks;
+  double   ms_upload, ms_kernel, ms_download, ms_total;
+} ckm_nearid_info;
+int  ckm_nearid_check(const ckm_nearid_args *a);
+int  ckm_nearid_host(const ckm_nearid_args *a, uint64_t budget_bytes, const ckm_nearid_out *out, ckm_nearid_info *info);
+int  ckm_nearid_run(ckm_ctx *ctx, const ckm_nearid_args *a, uint64_t budget_bytes, const ckm_nearid_out *out, ckm_nearid_info *info);
 
 /* ---- diagnostics used by the parity tests: every stage of one (model, sequence) pair, no filtering */
 typedef struct {
